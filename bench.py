@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py — the reference's benchmarks (runpeakbenchmark.sh / runsprotbenchmark.sh) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload peak|sprot-like] [--scaling strong|weak]
+    python bench.py --gpus N --steps K --warmup W [--workload peak|sprot-like] [--scaling strong|weak] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (a torch.distributed.run child,
@@ -24,17 +25,22 @@ Multi-GPU: `--scaling strong` (default): ONE DB is cut into char-balanced shards
 (partitionDBAmongstGpus, cudasw4.cuh:928-1004), rank r scans shard r; no data-path collective, the per-rank top-K
 lists are merged on the host of rank 0.  `--scaling weak`: every rank scans its own --db-size subjects.
 
+A plain run sets up, warms up, times --steps steps and prints the line (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step`, ...); `--dump-outputs DIR` writes what the last timed step returned (dump_outputs()).  Everything
+else is measured with `--full`:
+
 After the timed region every query is scanned once more and EVERY score is checked (peak: against the reference's
 golden scores in tests/golden/ref_scores.json; sprot-like: against the CPU oracle on the cpu_baseline sample, or
 packed-vs-int32 equality of all scores when there is no CPU leg) -> "verified".
 
-With N > 1 ranks the default (strong-scaling) line also carries `"weak_scaling": {...}`: the same benchmark with one full
-DB per rank.  The default (peak) run also measures the sprot-like workload afterwards and reports it as `"sprot_like": {...}` in the
+With N > 1 ranks the --full (strong-scaling) line also carries `"weak_scaling": {...}`: the same benchmark with one full
+DB per rank.  The --full (peak) run also measures the sprot-like workload afterwards and reports it as `"sprot_like": {...}` in the
 same line (its own timed region, verification, roofline and CPU leg), so that BASELINE config 3 is under the same clock.
 
-Prints ONE JSON line on rank 0 (driver contract), including `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0 (driver contract); with --full including `roofline` and `cpu_baseline`.
 """
 import argparse
+import contextlib
 import hashlib
 import json
 import os
@@ -76,6 +82,14 @@ def parse_args(argv=None):
     ap.add_argument("--top", type=int, default=10, help="top-K per query inside the timed region (reference scripts: 0)")
     ap.add_argument("--max-gpu-mem", default="0", help="per-GPU memory limit (K/M/G suffix); small values force batch streaming")
     ap.add_argument("--max-batch-bytes", default="0", help="batch size of the streamed part of a shard (K/M/G suffix; default 128M)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: verification of every score, the CPU baseline, roofline / per-kernel "
+                         "figures (HIP events, shader-clock sampling, device calibration), the Swiss-Prot-like secondary leg, the "
+                         "peak sweep, the shard-proxy legs and the multi-rank weak-scaling run.  Without it a run sets up, warms "
+                         "up, times --steps steps and prints the line; the --no-* switches below only matter with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (per query: the merged top-K scores "
+                         "and ids, the overflow / re-score counts) as DIR/<name>.npy in float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="peak workload: skip the Swiss-Prot-like secondary measurement")
@@ -93,8 +107,13 @@ def parse_args(argv=None):
                          "uniprot_sprot, runsprotbenchmark.sh:18-51) instead of the synthetic stand-in; default: "
                          "$CUDASW4_SPROT_PREFIX")
     ap.add_argument("--kernel-table", action="store_true",
-                    help="add the per-kernel table of the timed region to the line (tools/collect_profiles.sh matches it with the PMC passes)")
-    return ap.parse_args(argv)
+                    help="with --full: add the per-kernel table of the timed region to the line (tools/collect_profiles.sh matches it with the PMC passes)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        args.no_cpu_baseline = args.no_verify = args.no_secondary = args.no_sweep = args.no_shard_proxy = True
+    return args
 
 
 def parse_size(s):
@@ -576,7 +595,7 @@ def run_rank(args):
     env.numa_node, env.numa_bound = numa_node, bool(numa_bound)
     env.torch, env.dist, env.world, env.rank, env.local_rank = torch, dist, world, rank, local_rank
     env.distributed, env.backend, env.comm_dev = distributed, backend, comm_dev
-    out = measure(env, args, args.workload, want_cpu=not args.no_cpu_baseline and world == 1)
+    out = measure(env, args, args.workload, want_cpu=not args.no_cpu_baseline and world == 1, dump_dir=args.dump_outputs)
     if args.workload == "peak" and not args.no_secondary:
         # BASELINE config 3 under the same clock: the Swiss-Prot-like DB with the packed-int16 configuration, reported
         # next to the headline (its own timed region, verification and roofline; the CPU leg doubles as its checker)
@@ -802,9 +821,34 @@ def peak_sweep(env, args):
             "seconds": round(time.perf_counter() - t_begin, 1)}
 
 
-def measure(env, args, workload, want_cpu):
-    """One workload on this rank: load the DB shard, warm up, time `steps` steps, verify every score, build the JSON
-    object (returned on rank 0, None elsewhere)."""
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dump_dir, results, merged, K):
+    """--dump-outputs: what the last timed step handed its caller, per query — the merged top-K scores and ids (-1 where a
+    list is shorter than K) and this rank's overflow / re-score counts — as float64 DIR/<name>.npy.  Were the top-K lists
+    above 64 MB in all, a fixed, seeded sample of their columns is written instead."""
+    nq = len(results)
+    scores, ids = np.full((nq, K), -1.0), np.full((nq, K), -1.0)
+    for qi in range(nq if K > 0 else 0):
+        s, i = merged[qi]
+        scores[qi, :len(s)] = s
+        ids[qi, :len(i)] = i
+    cols = max(1, (DUMP_BUDGET_BYTES - (1 << 20)) // (16 * max(nq, 1)))   # (1 MB for the counts and the .npy headers)
+    if K > cols:
+        keep = np.sort(np.random.default_rng(0).choice(K, cols, replace=False))
+        scores, ids = scores[:, keep], ids[:, keep]
+    os.makedirs(dump_dir, exist_ok=True)
+    arrays = {"top_scores": scores, "top_ids": ids,
+              "num_overflows": np.array([r["num_overflows"] for r in results], dtype=np.float64),
+              "num_rescored": np.array([r["num_rescored"] for r in results], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dump_dir, name + ".npy"), a)
+
+
+def measure(env, args, workload, want_cpu, dump_dir=None):
+    """One workload on this rank: load the DB shard, warm up, time `steps` steps, write the last step's results to
+    `dump_dir` (rank 0), verify every score (--full), build the JSON object (returned on rank 0, None elsewhere)."""
     torch, dist, world, rank, local_rank = env.torch, env.dist, env.world, env.rank, env.local_rank
     distributed, comm_dev = env.distributed, env.comm_dev
     # inputs come from the product's own host library (FASTA reader, encoder, pseudo-DB generator);
@@ -874,6 +918,7 @@ def measure(env, args, workload, want_cpu):
 
     merged = [None] * len(queries)
     load = {"num_overflows": 0, "num_rescored": 0}  # of the last step: summed over its 20 queries (this rank's shard)
+    last = {}  # the last step's per-query results on this rank (--dump-outputs)
     # "always": every query submitted before the one before it is collected (multi-rank runs: small shards); "never": one
     # at a time; "rule": like `align` — two in flight exactly where the driver says the tail hand-over applies
     # (Driver.scan_stream: small resident shards, queries that are scanned in a few milliseconds)
@@ -893,6 +938,7 @@ def measure(env, args, workload, want_cpu):
         results = drv.scan_many(query_letters) if pipelined else drv.scan_stream(query_letters) if by_rule else [drv.scan(q) for q in query_letters]
         load["num_overflows"] = sum(r["num_overflows"] for r in results)
         load["num_rescored"] = sum(r["num_rescored"] for r in results)
+        last["results"] = results
         for qi, r in enumerate(results):
             n = len(r["scores"])
             mine[qi, :n, 0] = r["scores"]
@@ -922,22 +968,30 @@ def measure(env, args, workload, want_cpu):
         one_step()
     barrier()
     h2d_before = drv.streamed_bytes()
-    drv.record_kernel_events(True)
-    try:
-        bus = torch.cuda.get_device_properties(local_rank).pci_bus_id
-        bus = "%02x:" % int(bus) if isinstance(bus, int) else str(bus)
-    except Exception:
-        bus = None
-    with SclkSampler(bus) as sclk_sampler:
+    # --full: HIP events around every DP launch and the shader clock sampled during the timed region (roofline figures)
+    sclk_sampler = contextlib.nullcontext()
+    if args.full:
+        drv.record_kernel_events(True)
+        try:
+            bus = torch.cuda.get_device_properties(local_rank).pci_bus_id
+            bus = "%02x:" % int(bus) if isinstance(bus, int) else str(bus)
+        except Exception:
+            bus = None
+        sclk_sampler = SclkSampler(bus)
+    with sclk_sampler:
         t0 = time.perf_counter()
         for _ in range(args.steps):
             one_step()
         barrier()
         dt = time.perf_counter() - t0
-    drv.record_kernel_events(False)
-    sclk = sclk_sampler.summary()
-    events = drv.take_kernel_events()
+    sclk, events = None, []
+    if args.full:
+        drv.record_kernel_events(False)
+        sclk = sclk_sampler.summary()
+        events = drv.take_kernel_events()
     h2d_per_step = (drv.streamed_bytes() - h2d_before) // max(args.steps, 1)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, last["results"], merged, K)
 
     t = torch.tensor([dt], dtype=torch.float64, device=comm_dev)
     if distributed:
@@ -1061,9 +1115,11 @@ def measure(env, args, workload, want_cpu):
             # reference's "num overflows"), subjects the packed kernels flagged and a 32-bit kind re-scored (a few more:
             # the column-offset frame flags early), and the time of the re-score launches (HIP events, inside the timed region)
             "overflow_load": {"num_overflows": load["num_overflows"], "num_rescored": load["num_rescored"],
-                              "rescore_launches_per_step": sum(1 for e in events if e.get("rescore")) // max(args.steps, 1),
-                              "rescore_ms_per_step": round(sum(e["ms"] for e in events if e.get("rescore")) / max(args.steps, 1), 3)},
+                              "rescore_launches_per_step": sum(1 for e in events if e.get("rescore")) // max(args.steps, 1) if args.full else None,
+                              "rescore_ms_per_step": round(sum(e["ms"] for e in events if e.get("rescore")) / max(args.steps, 1), 3) if args.full else None},
         }
+        if not args.full:
+            out["verified_how"] = "not checked: a plain run times the steps only (--full verifies every score)"
         if args.kernel_table:
             out["kernels"] = ktable
         if want_cpu and cpu_obj is None:

@@ -7,7 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-#ifdef BINDING_ON_GPU   // the same block on real device buffers (tests/boundary/Makefile -> _build/binding_gpu)
+#ifdef BINDING_ON_GPU   // the same block on real device buffers (tests/boundary/Makefile -> oracle/_ref/boundary/binding_gpu)
 #include <hip/hip_runtime_api.h>
 #include <algorithm>
 #include <chrono>

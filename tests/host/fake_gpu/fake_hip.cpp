@@ -72,7 +72,8 @@ hipError_t hipDeviceGetAttribute(int* pi, hipDeviceAttribute_t attr, int) {
     *pi = attr == hipDeviceAttributeCanUseStreamWaitValue ? 1 : attr == hipDeviceAttributeMultiprocessorCount ? 256 : 0;
     return hipSuccess;
 }
-hipError_t hipDeviceGetPCIBusId(char* s, int len, int device) { snprintf(s, size_t(len), "0000:%02x:00.0", 0xc1 + device * 0x10); return hipSuccess; }
+// (PCI domain ffff, function 7: an address no real GPU host has, so that the fake devices' NUMA node stays unknown on any box)
+hipError_t hipDeviceGetPCIBusId(char* s, int len, int device) { snprintf(s, size_t(len), "ffff:%02x:00.7", 0xc1 + device * 0x10); return hipSuccess; }
 hipError_t hipDeviceGetStreamPriorityRange(int* lo, int* hi) { *lo = 1; *hi = -1; return hipSuccess; }
 hipError_t hipMemGetInfo(size_t* f, size_t* t) { *f = size_t(64) << 30; *t = size_t(64) << 30; return hipSuccess; }
 

@@ -33,6 +33,41 @@ def test_bench_spawn_command_and_defaults():
     assert b.parse_size("1G") == 1 << 30 and b.parse_size("0") == 0
 
 
+def test_bench_plain_run_and_full_switch():
+    """Without --full a run is the headline alone (every extra leg off); --full leaves the --no-* switches to the caller;
+    --steps is the number of timed steps and must be at least 1."""
+    b = load_bench()
+    plain = b.parse_args(["--steps", "7", "--warmup", "2"])
+    assert not plain.full and plain.steps == 7 and plain.warmup == 2 and plain.dump_outputs is None
+    assert plain.no_cpu_baseline and plain.no_verify and plain.no_secondary and plain.no_sweep and plain.no_shard_proxy
+    full = b.parse_args(["--full", "--no-sweep", "--dump-outputs", "out"])
+    assert full.full and full.no_sweep and full.dump_outputs == "out"
+    assert not (full.no_cpu_baseline or full.no_verify or full.no_secondary or full.no_shard_proxy)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True)
+    assert p.returncode == 2 and "--steps" in p.stderr
+
+
+def test_bench_dump_outputs_writes_the_last_steps_lists(tmp_path):
+    """--dump-outputs: per query the merged top-K scores / ids (-1 past a short list) and the overflow counts, float64;
+    a top-K too large for the 64 MB budget is written as a fixed, seeded sample of its columns."""
+    b = load_bench()
+    results = [{"num_overflows": 1, "num_rescored": 2}, {"num_overflows": 0, "num_rescored": 0}]
+    merged = [(np.array([50, 40, 30], np.int32), np.array([7, 3, 9])), (np.array([20], np.int32), np.array([4]))]
+    b.dump_outputs(str(tmp_path / "d"), results, merged, 3)
+    got = {n: np.load(str(tmp_path / "d" / (n + ".npy"))) for n in ("top_scores", "top_ids", "num_overflows", "num_rescored")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["top_scores"].tolist() == [[50, 40, 30], [20, -1, -1]] and got["top_ids"].tolist() == [[7, 3, 9], [4, -1, -1]]
+    assert got["num_overflows"].tolist() == [1, 0] and got["num_rescored"].tolist() == [2, 0]
+    K = 3_000_000
+    big = [(np.arange(K, 0, -1, dtype=np.int32), np.arange(K))] * 2
+    for d in ("e", "f"):
+        b.dump_outputs(str(tmp_path / d), results, big, K)
+    total = sum(os.path.getsize(str(tmp_path / "e" / f)) for f in os.listdir(str(tmp_path / "e")))
+    assert total <= 64 << 20
+    e, f = np.load(str(tmp_path / "e" / "top_ids.npy")), np.load(str(tmp_path / "f" / "top_ids.npy"))
+    assert e.shape[1] < K and np.array_equal(e, f) and (np.diff(e[0]) > 0).all()
+
+
 def test_roofline_arithmetic_uses_the_device_and_the_measured_peaks():
     """VERDICT r4 item 5: the VALU peak comes from the device's own CU count, the in-process micro-run and the sampled clock;
     nothing is hard-coded but the nominal clock, which is named."""

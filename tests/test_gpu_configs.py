@@ -133,14 +133,36 @@ def test_streaming_pinned_fallback_matches(monkeypatch):
         d.close()
 
 
-def run_bench(extra, env_extra=None):
+def run_bench(extra, env_extra=None, full=True):
+    """One bench.py line; full=True (what the checks below read: verification, roofline, secondary legs) adds --full."""
     env = dict(os.environ)
     env.update(env_extra or {})
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True, env=env,
-                       timeout=900)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + (["--full"] if full else []) + extra, capture_output=True,
+                       text=True, env=env, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
     return json.loads(line)
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) is the headline alone: its line carries the contract's fields and none of the
+    --full legs; --dump-outputs writes the last timed step's top-K lists — every score the reference's golden score, the
+    K lowest ids (all subjects tie) — and a second run with other step counts writes the same arrays."""
+    common = ["--db-size", "100000"]
+    out = run_bench(["--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "a")] + common, full=False)
+    assert out["metric"] == "GCUPS" and out["unit"] == "GCUPS" and out["higher_is_better"] is True and out["dtype"] == "f16x2"
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and out["steps"] == 2 and out["warmup"] == 1
+    assert out["verified"] is None and out["cpu_baseline"] is None and out["roofline"] is None
+    assert not {"sprot_like", "peak_sweep", "shard_proxy", "weak_scaling"} & set(out)
+    golden = O.golden("ref_scores.json")["pseudo"]["512"]
+    a = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in ("top_scores", "top_ids", "num_overflows", "num_rescored")}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert a["top_scores"].shape == a["top_ids"].shape == (20, 10) and a["num_overflows"].shape == (20,)
+    assert (a["top_scores"] == np.asarray(golden, dtype=np.float64)[:, None]).all()
+    assert (a["top_ids"] == np.arange(10)[None, :]).all() and (a["num_rescored"] == 0).all()
+    run_bench(["--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path / "b")] + common, full=False)
+    for n, v in a.items():
+        assert np.array_equal(np.load(str(tmp_path / "b" / (n + ".npy"))), v), n
 
 
 def test_bench_two_ranks_on_one_gpu_strong_and_weak():
@@ -202,7 +224,7 @@ def test_bench_process_group_path_with_the_real_backend():
     env = dict(os.environ, BENCH_FORCE_DIST="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0",
-           "--db-size", "100000", "--no-cpu-baseline", "--no-secondary"]
+           "--db-size", "100000", "--no-cpu-baseline", "--no-secondary", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])

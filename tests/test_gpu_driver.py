@@ -423,9 +423,9 @@ def test_documented_binding_runs_on_the_gpu(dpx):
     against the reference's own headers where they lie (tests/boundary/Makefile; the binary travels to the GPU box) — EXECUTED:
     contexts, matrix, query, the partition walk, overflow re-score and top-K on real device buffers holding the reference's
     all-vs-all DB; every score and the top-5 equal the golden values generated from the reference's own DP."""
-    exe = os.path.join(O.ROOT, "tests", "boundary", "_build", "binding_gpu")
+    exe = os.path.join(O.ROOT, "oracle", "_ref", "boundary", "binding_gpu")
     if not os.path.exists(exe):
-        pytest.skip("tests/boundary/_build/binding_gpu is built where /root/reference exists (__graft_entry__.build())")
+        pytest.skip("oracle/_ref/boundary/binding_gpu is built only where the reference tree exists (__graft_entry__.build())")
     g = O.golden("ref_scores.json")
     for qi in (2, 9, 16, 19):
         p = subprocess.run([exe, GOLDEN_DB, str(qi)] + (["DPX"] if dpx else []), capture_output=True, text=True, timeout=300)

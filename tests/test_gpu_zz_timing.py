@@ -111,9 +111,9 @@ def test_documented_binding_runs_at_the_host_drivers_rate():
     the host driver on the same arrays: the same top scores, and a rate close to the driver's — at a quarter of the size the driver keeps two queries in flight,
     which a per-batch binding does not: 0.98 / 0.92 measured, asserted with a margin for run-to-run spread; at full size 1.00 /
     1.01 (profiles/r06_binding_bench.txt); the launcher-by-launcher form of the same document is reported beside it."""
-    exe = os.path.join(ROOT, "tests", "boundary", "_build", "binding_gpu")
+    exe = os.path.join(ROOT, "oracle", "_ref", "boundary", "binding_gpu")
     if not os.path.exists(exe):
-        pytest.skip("tests/boundary/_build/binding_gpu is built where /root/reference exists (__graft_entry__.build())")
+        pytest.skip("oracle/_ref/boundary/binding_gpu is built only where the reference tree exists (__graft_entry__.build())")
     import importlib.util
     spec = importlib.util.spec_from_file_location("binding_bench", os.path.join(ROOT, "tools", "binding_bench.py"))
     bb = importlib.util.module_from_spec(spec)

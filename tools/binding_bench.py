@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Speed of the DOCUMENTED boundary against the host driver on the same DBs.
 
-tests/boundary/_build/binding_gpu is the reference-side binding — the verbatim code block of INTEGRATION.md, compiled against
+oracle/_ref/boundary/binding_gpu is the reference-side binding — the verbatim code block of INTEGRATION.md, compiled against
 the reference's own headers — with a --bench mode: every query of allqueries.fasta through the documented per-query block
 (sw_set_query + sw_scan_batch + sw_batch_join + sw_topk), and through the launcher-by-launcher form (one sw_scan_partition per
 length partition, sw_rescore_overflow, sw_topk) beside it.  The host driver (libcudasw4_host.so, what bench.py measures) scans
@@ -21,7 +21,7 @@ import numpy as np
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
-EXE = os.path.join(ROOT, "tests", "boundary", "_build", "binding_gpu")
+EXE = os.path.join(ROOT, "oracle", "_ref", "boundary", "binding_gpu")
 
 
 def write_db(prefix, chars, offsets, lengths):

@@ -25,7 +25,7 @@ export CUDASW4_AMD_RESCORE_SERVICE=0
 # (hipStreamWaitValue32) never got released (the Swiss-Prot-like passes hung until their timeout); with one kernel at a
 # time there is nothing to run beside anyway
 export CUDASW4_AMD_NO_HANDSHAKE=1
-BENCH="bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-verify --no-secondary --kernel-table $EXTRA"
+BENCH="bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-verify --no-secondary --kernel-table $EXTRA"
 PASSES=${PASSES:-"stats traffic valu lds clock"}
 has() { case " $PASSES " in *" $1 "*) return 0;; *) return 1;; esac; }
 if has stats; then

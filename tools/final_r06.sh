@@ -10,7 +10,7 @@ timeout 3000 python -m pytest tests -m gpu -q 2>&1 | tail -15 > $O/pytest_gpu.tx
 tail -2 $O/pytest_gpu.txt
 bash tools/collect_all_profiles.sh r06 $COMMIT > $O/collect.log 2>&1
 tail -3 $O/collect.log
-( time timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_default_time.txt
+( time timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_default_time.txt
 tail -3 $O/bench_default_time.txt
 timeout 1500 python tools/binding_bench.py > $O/binding_bench.txt 2>&1
 cat $O/binding_bench.txt | tail -3

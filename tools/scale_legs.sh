@@ -9,7 +9,7 @@
 N=${1:-60000000}; TAG=${2:-r04}
 OUT=gpurun_out/scale_$TAG; mkdir -p $OUT
 Q="--queries 0,9,19 --steps 1 --warmup 1 --no-secondary --no-sweep --cpu-sample-subjects 3000"
-run() { name=$1; shift; echo "== $name: $*"; ( time python bench.py --workload uniref50-like --db-size $N $Q "$@" ) > $OUT/$name.json 2> $OUT/$name.err; tail -c 400 $OUT/$name.json; grep real $OUT/$name.err; }
+run() { name=$1; shift; echo "== $name: $*"; ( time python bench.py --full --workload uniref50-like --db-size $N $Q "$@" ) > $OUT/$name.json 2> $OUT/$name.err; tail -c 400 $OUT/$name.json; grep real $OUT/$name.err; }
 run config4_half2_resident_1shard
 run config4_half2_resident_8shards --shards-per-gpu 8
 run config5_int32_hybrid_16G --kernel dpxs32 --max-gpu-mem 16G
