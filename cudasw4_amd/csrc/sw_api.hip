@@ -171,7 +171,7 @@ struct sw_ctx {
     int query_next = 0;
     int32_t qlen = 0;
     bool have_query = false;
-    Profile profiles[4][4][2];  // [kind][shape: 0 = 16-lane groups, 1 = 64-lane groups, 2 = 8-lane groups, 3 = 4-lane groups][plain | column-offset recurrence]
+    Profile profiles[4][4][3];  // [kind][shape: 0 = 16-lane groups, 1 = 64-lane groups, 2 = 8-lane groups, 3 = 4-lane groups][plain | column frame | uniform frame]
     bool use_offs = true;        // CUDASW4_AMD_NO_OFFS=1: always the plain recurrence (A/B measurements)
     int64_t long16_min = -1;     // sw_set_long16_min: partition 34 gets 16-lane groups from this many subjects up (-1: 512)
     int64_t long16_min_default = -1;  // the built-in rule (sw_set_long16_min(ctx, -1) returns to it)
@@ -261,8 +261,9 @@ int lanes_for_partition_any(const sw_ctx* ctx, int kind, int part_id, int32_t n,
 }
 
 
-int ensure_profile(sw_ctx* ctx, int kind, int lanes, bool offs, int shift, hipStream_t stream) {
-    Profile& pr = ctx->profiles[kind][shape_index(lanes)][offs];
+// frame: 0 plain recurrence, 1 column frame, 2 uniform frame (swk::uniform_frame_launch: row 0's profile entries a higher)
+int ensure_profile(sw_ctx* ctx, int kind, int lanes, int frame, int shift, hipStream_t stream) {
+    Profile& pr = ctx->profiles[kind][shape_index(lanes)][frame];
     if (pr.valid && pr.shift != shift) pr.valid = false;  // other gap-extension score than last time
     if (pr.valid) {
         // built on another stream earlier in this query: order this stream after the build
@@ -283,7 +284,7 @@ int ensure_profile(sw_ctx* ctx, int kind, int lanes, bool offs, int shift, hipSt
         SW_HIP(hipMalloc(&pr.dev, cap));
         pr.capacity = cap;
     }
-    SW_HIP(kl->profile(pl.rows, lanes, ctx->d_query, ctx->qlen, ctx->d_matrix, ctx->dim, pl.nstripes, pr.dev, shift, stream));
+    SW_HIP(kl->profile(pl.rows, lanes, ctx->d_query, ctx->qlen, ctx->d_matrix, ctx->dim, pl.nstripes, pr.dev, shift, frame == 2 ? 1 : 0, stream));
     pr.shift = shift;
     if (!pr.ready) SW_HIP(hipEventCreateWithFlags(&pr.ready, hipEventDisableTiming));
     SW_HIP(hipEventRecord(pr.ready, stream));
@@ -441,9 +442,14 @@ int scan_common(sw_ctx* ctx, int kind, int lanes, const int8_t* chars, const uin
     int64_t K = 0;
     const bool offs = offs_possible(ctx, kind, lanes, max_subject_len, gop, gex, ovf_check, &K);
     if (kind_packed(kind) && !offs) return fail(SW_ERR_INVALID, "internal: a packed launch without the column-offset recurrence (packed_fallback_kind)");
-    int rc = ensure_profile(ctx, kind, lanes, offs, offs ? a : 0, stream);
+    // the frame of the kernel that will run (sw_launch.hpp: uniform_frame_launch) selects the profile
+    const QueryPlan plan0 = plan_query(kind, ctx->qlen, lanes);
+    const StreamPlan sp = stream_plan(ctx, kind, lanes, a, plan0, max_subject_len);
+    const bool uniform = swk::uniform_frame_launch(kl->packed, offs, lanes, plan0.nstripes > 1, sp.slots);
+    const int frame = offs ? (uniform ? 2 : 1) : 0;
+    int rc = ensure_profile(ctx, kind, lanes, frame, offs ? a : 0, stream);
     if (rc != SW_OK) return rc;
-    const Profile& prof = ctx->profiles[kind][shape_index(lanes)][offs];
+    const Profile& prof = ctx->profiles[kind][shape_index(lanes)][frame];
     const QueryPlan pl = prof.plan;
     const bool multi = pl.nstripes > 1;
 
@@ -477,8 +483,8 @@ int scan_common(sw_ctx* ctx, int kind, int lanes, const int8_t* chars, const uin
         }
         p.gex_mag = a;
         {   // row classes of the kernel that plan (rows, lanes) selects: lowering words at the class wrap / the last row
-            const int P = swk::frame_classes(kl->packed, pl.rows, lanes, multi);
-            const int wrap = -a * P, wrap_last = -a * ((pl.rows - 1) % P + 1);
+            const int P = swk::frame_classes(kl->packed, pl.rows, lanes, multi, uniform);
+            const int wrap = -a * P, wrap_last = -a * ((pl.rows - 1) % P + (uniform ? 0 : 1));
             switch (kind) {
                 case SW_KIND_F16X2: p.wrap_class = swk::Arith<swk::F16X2>::encode_gap(wrap); p.wrap_last = swk::Arith<swk::F16X2>::encode_gap(wrap_last); break;
                 case SW_KIND_I16X2: p.wrap_class = swk::Arith<swk::I16X2>::encode_gap(wrap); p.wrap_last = swk::Arith<swk::I16X2>::encode_gap(wrap_last); break;
@@ -486,6 +492,9 @@ int scan_common(sw_ctx* ctx, int kind, int lanes, const int8_t* chars, const uin
                 default: p.wrap_class = swk::Arith<swk::F32>::encode_gap(wrap); p.wrap_last = swk::Arith<swk::F32>::encode_gap(wrap_last); break;
             }
         }
+        // the uniform frame's period is bounded by its level table (a quarter of a percent of lowering steps at the bound)
+        p.flag_period = (int32_t)K;
+        if (uniform) K = std::min<int64_t>(K, swk::kUniformMaxPeriod);
         p.renorm_quads = (int32_t)(K / 4);
         const int lower = -(int)((int64_t)a * K);
         switch (kind) {
@@ -494,9 +503,14 @@ int scan_common(sw_ctx* ctx, int kind, int lanes, const int8_t* chars, const uin
             case SW_KIND_I32: p.renorm_word = swk::Arith<swk::I32>::encode_gap(lower); break;
             default: p.renorm_word = swk::Arith<swk::F32>::encode_gap(lower); break;
         }
+        if (uniform) {
+            p.uniform_frame = 1;
+            for (int u = 0; u < swk::kLevelWords; u++)
+                p.levels[u] = kind == SW_KIND_F16X2 ? swk::Arith<swk::F16X2>::zero_at(a, std::min<int>(u, (int)K + 16))
+                                                    : swk::Arith<swk::I16X2>::zero_at(a, std::min<int>(u, (int)K + 16));
+        }
     }
     // Streamed subjects (sw_stream_kernel.hpp): packed kinds on 16-lane groups, column-offset recurrence, plain ranges
-    const StreamPlan sp = stream_plan(ctx, kind, lanes, a, pl, max_subject_len);
     if (sp.slots >= 1) {
         p.stream_slots = sp.slots; p.stream_cols = sp.cols; p.stream_room = sp.room; p.level_base = sp.base;
         p.jump = sp.jump; p.jump_limit = sp.jump - 4;

@@ -24,7 +24,10 @@
 //     |gex| * (j mod K + LANES), which takes the "+ gex" out of the horizontal gap state, and lane-local row r by a
 //     further |gex| * (r mod P) (row classes), which takes it out of the vertical gap state except where the class
 //     wraps: 5.8 instead of 8.5 instructions per cell pair; the plain form remains for gap-extension scores too
-//     large for any K;
+//     large for any K.  The packed sw_scan_kernel runs it in the UNIFORM frame instead: a cell of step t of stripe s is
+//     raised by |gex| * ((t + LANES*s) mod K + 1 + class), the same zero levels in every lane of the wave — held in scalar
+//     registers, the frame lowered by every lane in the same step (sw_scan_kernel explains the constants); the streamed
+//     kernels keep the column frame;
 //   * queries longer than one stripe are processed stripe after stripe by the same group; the H/F
 //     row at the stripe border is spilled to a small global scratch (branch-free: 8 bytes stored per
 //     step, 32 bytes loaded per four steps), the analogue of the reference's devTempHcol2/devTempEcol2;
@@ -159,6 +162,10 @@ struct Arith<I16X2> {
     // the zero level v (sw_stream_kernel.hpp: levels with a base and jumps) in both halves
     static __device__ __forceinline__ u32 level_word(int v) { const u32 z = (u32)(kBias + v) & 0xffffu; return z | (z << 16); }
     static __device__ __forceinline__ u32 true_of(u32 m, u32 z) { return gap(m, z); }  // plain unsigned integers
+    // frame lowering by the magnitude word w (saturating: see sw_scan_kernel's lower_frame for the one value it can reach)
+    static __device__ __forceinline__ u32 lower(u32 a, u32 w) {
+        return __builtin_bit_cast(u32, __builtin_elementwise_sub_sat(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, w)));
+    }
     static __device__ __forceinline__ u32 true_max(u32 a, u32 b) {
         return __builtin_bit_cast(u32, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
     }
@@ -220,6 +227,7 @@ struct Arith<F16X2> {
     static __device__ __forceinline__ u32 true_of(u32 m, u32 z) {
         return __builtin_bit_cast(u32, (f16x2)(__builtin_bit_cast(f16x2, m) - __builtin_bit_cast(f16x2, z)));
     }
+    static __device__ __forceinline__ u32 lower(u32 a, u32 w) { return add(a, w); }  // w = encode_gap(-a*K)
     static __device__ __forceinline__ u32 true_max(u32 a, u32 b) { return max2(a, b); }
     static __device__ __forceinline__ int true_lo(u32 v) { return score_lo(v); }
     static __device__ __forceinline__ int true_hi(u32 v) { return score_hi(v); }
@@ -372,6 +380,10 @@ struct Geometry {
     static_assert(kPadLetter * kLetterUnits < 256, "letter offset must fit a byte");
 };
 
+// Uniform frame (packed sw_scan_kernel: ScanParams::uniform_frame): longest frame period and the entries of the level table
+constexpr int kUniformMaxPeriod = 256;
+constexpr int kLevelWords = kUniformMaxPeriod + 16;
+
 struct ScanParams {
     const int8_t* chars;
     const uint64_t* offsets;
@@ -394,10 +406,10 @@ struct ScanParams {
     const u32* zeros;          // >= 64 bytes of the kind's zero pattern (border of the first stripe)
     u32* work_counter;         // zeroed before the launch: next batch to hand out
     int32_t gex_mag;           // OFFS kernels: a = -gex; then gop holds encode_gap(gop - gex) and the profile s + a
-    int32_t renorm_quads;      // OFFS: K/4 — every K columns a lane lowers its frame by a*K (0: never); a power of two
+    int32_t renorm_quads;      // OFFS: K/4 — the frame is lowered by a*K every K columns (uniform frame: every K steps; 0: never); a power of two
     u32 renorm_word;           // encode_gap(-a*K)
     u32 wrap_class;            // OFFS: encode_gap(-a*P), P = frame_classes(...) of the launched kernel (dp_step: row classes)
-    u32 wrap_last;             // OFFS: encode_gap(-a*((R-1) % P + 1))
+    u32 wrap_last;             // OFFS: encode_gap(-a*((R-1) % P + 1)); uniform frame: encode_gap(-a*((R-1) % P))
     int32_t* stat_count;       // optional.  Scan launches (streamed kernels): += subjects listed only because the slot before them
                                // scored at or above the zero-level jump (sw_set_dirty_counter).  Re-score launches: += subjects whose exact score is >= stat_limit, i.e. the
     int32_t stat_limit;        // reference's notion of an overflow (half2_kernels.cuh:1087-1109), for the printed statistic
@@ -435,6 +447,11 @@ struct ScanParams {
     int32_t jump;
     u32 jump_word;
     int32_t jump_limit;
+    // Uniform frame (OFFS packed sw_scan_kernel, which needs a profile built with head_extra = 1): levels[u] = the zero level
+    // a*u in the kind's packed encoding (Arith::zero_at), u <= K + P; the kernel reads its window with scalar loads
+    int32_t uniform_frame;
+    int32_t flag_period;       // the column frame's period K (offs_possible): the uniform frame flags at least what it would
+    u32 levels[kLevelWords];
 };
 
 constexpr int32_t kListEmpty = -1, kListTaken = -2;
@@ -507,12 +524,15 @@ __device__ __forceinline__ void lds_read_words(u32 (&dst)[NW], const unsigned ch
 #ifndef SWK_CLASSES_SCALAR
 #define SWK_CLASSES_SCALAR 4
 #endif
-constexpr int frame_classes(bool packed, int R, int lanes, bool multi) {
+constexpr int frame_classes(bool packed, int R, int lanes, bool multi, bool uniform = false) {
     (void)lanes;
     // packed kinds: 8 classes for the tall kernels (two waves per SIMD anyway: 0.125 instead of 0.25 wrap subtractions per
-    // cell pair for 8 more registers, +0.8 % on the peak benchmark); the single-stripe kernels up to R = SWK_WAVES3_MAX_R and
-    // everything below R = 25 four, which keeps those at three (or more) waves per SIMD.  32-bit kinds: four (register-bound by their occupancy).
-    const int want = packed ? ((R > SWK_WAVES3_MAX_R || (multi && R >= 25 && R > SWK_WAVES3_MAX_R_MULTI)) ? SWK_CLASSES_PACKED : SWK_CLASSES_PACKED_SMALL)
+    // cell pair for 8 more registers, +0.8 % on the peak benchmark) and for the uniform-frame multi-stripe kernels from R = 25
+    // on (their zero levels live in scalar registers: the registers of the column frame's level window pay for the four more
+    // classes at three waves per SIMD — 779 instead of 791 VALU per quad at R = 32, no scratch access in the loop); the
+    // single-stripe kernels up to R = SWK_WAVES3_MAX_R and everything below R = 25 four, which keeps those at three (or more)
+    // waves per SIMD.  32-bit kinds: four (register-bound by their occupancy).
+    const int want = packed ? ((R > SWK_WAVES3_MAX_R || (multi && R >= 25 && (uniform || R > SWK_WAVES3_MAX_R_MULTI))) ? SWK_CLASSES_PACKED : SWK_CLASSES_PACKED_SMALL)
                             : SWK_CLASSES_SCALAR;
     int P = want;
     while (P > 1 && 2 * P > R) P--;  // at least two rows per class, so that the running maximum still folds two rows per max3
@@ -576,11 +596,13 @@ struct StripeState {
 // `first` (MULTI): the stripe has no predecessor, lane 0's boundary is the zero level instead of the border row.
 // ZFILL = false (sw_stream_kernel.hpp): the head lane's vertical gap state is the column's zero level (class 0) instead of the
 // bound_ctrl zero fill — levels that start below zero, and separator columns, which rebuild a lane's state from it.
-template <int KIND, int R, int LANES, int BYTE, bool MULTI, bool OFFS = false, int P = 1, bool ZFILL = true>
+// UNI (sw_scan_kernel, packed kinds): the uniform frame — the zero levels depend on the step alone and come from the caller's
+// wave-uniform window zw (scalar registers) instead of st.Zc (sw_scan_kernel explains the frame).
+template <int KIND, int R, int LANES, int BYTE, bool MULTI, bool OFFS = false, int P = 1, bool ZFILL = true, bool UNI = false>
 __device__ __forceinline__ void dp_step(StripeState<KIND, R, P>& st, const unsigned char* tile,
                                         u32 lettersA, u32 lettersB, u32 gop, u32 gex, u32 inH, u32 inF,
                                         u32 apos = 0, bool first = false, u32 wrapP = 0, u32 wrapLast = 0, bool head = false,
-                                        u32 laneStep = 0) {
+                                        u32 laneStep = 0, const u32* zw = nullptr) {
     using A = Arith<KIND>;
     using G = Geometry<KIND, R, LANES>;
     // what a lane adds to the LDS address it receives: one 16-byte slot.  8-lane groups: the second group of a DPP row
@@ -636,7 +658,7 @@ __device__ __forceinline__ void dp_step(StripeState<KIND, R, P>& st, const unsig
             upH = prev_lane<LANES, false>(inH, st.Hlast, head);
             F = prev_lane<LANES, false>(inF, st.Fout, head);
         } else {
-            const u32 bH = st.Zc[Q + kLastClass];  // the local-alignment boundary H = 0 as row 0's diagonal expects it
+            const u32 bH = UNI ? zw[Q + kLastClass] : st.Zc[Q + kLastClass];  // the local-alignment boundary H = 0 as row 0's diagonal expects it
             upH = prev_lane<LANES, false>(bH, st.Hlast, head);
             // any F below the column's zero level is "no vertical gap": bound_ctrl zero fill (pattern 0 is below every
             // zero level of every kind, and the fp16 comparator of the int16 kind orders +0.0 below all its patterns)
@@ -700,7 +722,7 @@ __device__ __forceinline__ void dp_step(StripeState<KIND, R, P>& st, const unsig
 #pragma unroll
         for (int r = 0; r < R; r++) {
             const int c = r % P;
-            const u32 zop = st.Zc[Q + c + 1];
+            const u32 zop = UNI ? zw[Q + c + 2] : st.Zc[Q + c + 1];
             if constexpr (G::kWide) {
                 if (r % 4 == 0) __builtin_amdgcn_sched_barrier(0);
                 if (CH::starts_chunk(r) && CH::chunk_of(r) + kChunks0 < kChunksAll)
@@ -724,9 +746,9 @@ __device__ __forceinline__ void dp_step(StripeState<KIND, R, P>& st, const unsig
             }
             const u32 fm = A::max3(F, hg, zop);
             st.E[r] = A::max3(st.E[r], hg, zop);
-            if (c == P - 1) F = A::gap(fm, wrapP);          // class P-1 -> class 0: lower by a*P
-            else if (r == R - 1) F = A::gap(fm, wrapLast);  // the lane's last row: back to class 0 for the next lane
-            else F = fm;                                     // next class: frame rises by a while F decays by a
+            if (r == R - 1) F = (UNI && kLastClass == 0) ? fm : A::gap(fm, wrapLast);  // the lane's last row: to class 0 of the next lane
+            else if (c == P - 1) F = A::gap(fm, wrapP);  // class P-1 -> class 0: lower by a*P
+            else F = fm;                                  // next class: frame rises by a while F decays by a
             if ((r / P) & 1) m[c] = A::fold2(m[c], st.H[r - P], h);
             else if (r + P >= R) m[c] = A::max2(m[c], h);
             st.H[r] = h;
@@ -921,7 +943,7 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
     using BD = Border<LANES>;
     constexpr int SHL1 = Shift<LANES>::kShl1;
     constexpr int kQuadsPerLetterBlock = LANES;  // a lane holds 4 letters: LANES quads per reload
-    constexpr int P = OFFS ? frame_classes(A::kPacked, R, LANES, MULTI) : 1;  // row classes of the column-offset frame
+    constexpr int P = OFFS ? frame_classes(A::kPacked, R, LANES, MULTI, OFFS && A::kPacked) : 1;  // row classes of the column-offset frame
     __shared__ __attribute__((aligned(16))) unsigned char lds[16 + G::kTileBytes];
     __shared__ __attribute__((aligned(16))) unsigned char rings[MULTI ? BD::ring_bytes(kGroups) : 16];
 
@@ -958,15 +980,26 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
     unsigned char* const ringOut = ringIn + BD::kInBytes;
     u32* const gBorder = MULTI ? p.scratch + ((size_t)blockIdx.x * kGroups + group) * (size_t)border_region_words<LANES>(p.lcap) : nullptr;
 
-    // OFFS: a lane starts every stripe "at column -lane": zero level a*(LANES - lane), +a per step
+    // The frame of the column-offset recurrence (dp_step<OFFS>).
+    //   * 32-bit kinds: the column frame — a cell of column j is raised by a*(j + LANES), a lane starts every stripe "at
+    //     column -lane" (zero level a*(LANES - lane)) and keeps its own zero levels (st.Zc); no lowering (a 32-bit frame has
+    //     room for any subject);
+    //   * packed kinds: the UNIFORM frame — a cell of step t of stripe s is raised by a*(u + 1 + class), u = t_g mod K with
+    //     t_g = t + LANES*s the global anti-diagonal.  A lane's column is t - lane, so the frame of a cell is a function of
+    //     its column and its global lane index LANES*s + lane: from column j to j + 1 the frame rises by a (E needs no
+    //     addition), the row classes work as in the column frame, a hand-off to the next lane (same column, one step
+    //     later) raises it by a*(1 - lastClass) (F: wrap_last = a*lastClass; row 0's diagonal, two steps back: the profile
+    //     carries a*(2 - lastClass), head_extra = 1), and a stripe border is one more such hand-off: t_g continues across it,
+    //     the border rings need no correction.  The zero levels are the same in every lane of the wave: a window zw of
+    //     P + 5 words in scalar registers, zw[k] = a*(u0 + k) with u0 the u of the quad's first step (ScanParams::levels),
+    //     and at u = K - 1 every lane lowers all it holds by a*K in the same step, after the quad's last step.
+    constexpr bool kUni = OFFS && A::kPacked;
     const u32 apos = OFFS ? A::pos_word(p.gex_mag) : 0u;
     const u32 apos4 = OFFS ? A::pos_word(4 * p.gex_mag) : 0u;
-    // frame lowering exists in the packed kernels only: a 32-bit frame has room for any subject (a second copy of the
-    // loop body would only cost the occupancy-bounded 32-bit kernels registers)
-    constexpr bool kLowers = OFFS && A::kPacked;
-    const int rq = kLowers ? p.renorm_quads : 0;
-    const u32 zstart = OFFS ? A::zero_at(p.gex_mag, LANES - lane) : A::kZero;
-    const u32 zbefore = OFFS ? A::zero_at(p.gex_mag, LANES - lane - 1) : A::kZero;  // the column before
+    const int rq = kUni ? p.renorm_quads : 0;
+    const int kmask = 4 * rq - 1;   // kUni: u = t_g & kmask
+    const u32 zstart = (OFFS && !kUni) ? A::zero_at(p.gex_mag, LANES - lane) : A::kZero;
+    const u32 zbefore = (OFFS && !kUni) ? A::zero_at(p.gex_mag, LANES - lane - 1) : A::kZero;  // the column before
 
     __shared__ int next_batch, batch_avail;
     // an entry of a claimed list: wait (briefly: the producer stores it right after it has counted it) until it is written,
@@ -1066,7 +1099,29 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
                 __syncthreads();
             }
             StripeState<KIND, R, P> st;
-            {
+            // kUni: the level window of the quad to come (scalar loads from the kernel arguments).  Used as operands right after
+            // the loads, so that the wait for them falls here and not among the LDS reads of the next step.
+            u32 zw[P + 5];
+            const int tg0 = kUni ? __builtin_amdgcn_readfirstlane(LANES * stripe) : 0;   // t_g of the stripe's first step
+            auto load_levels = [&](int q) {
+                const int u0 = __builtin_amdgcn_readfirstlane((tg0 + 4 * q) & kmask);
+#pragma unroll
+                for (int k = 0; k < P + 5; k++) zw[k] = p.levels[u0 + k];
+#pragma unroll
+                for (int k = 0; k < P + 5; k++) asm volatile("" : "+s"(zw[k]));
+            };
+            if constexpr (kUni) {
+                load_levels(0);
+                // the state before the first step (t_g0 - 1): H at its zero level, E at the level of the first step
+#pragma unroll
+                for (int r = 0; r < R; r++) { st.H[r] = zw[r % P]; st.E[r] = zw[r % P + 1]; }
+                // upH_prev: the boundary H(row above, column before) of the first step's row 0 — the previous lane's last row
+                // two steps back, one level below zw[lastClass] (fp16: may be -a; int16: >= 1024 - a)
+                st.upH_prev = A::gap(zw[(R - 1) % P], p.gex); st.Hlast = zw[(R - 1) % P]; st.Fout = zw[0];
+                // accumulator d holds the cells of frame zw[d + 1] (step q, class c: d = q + c); true score -> that frame
+#pragma unroll
+                for (int d = 0; d < P + 3; d++) st.maxv[d] = A::add(maxv, zw[d + 1]);
+            } else {
                 // zero levels of the column before the lane's first one, per class (zc[k] = zbefore + a*k)
                 u32 zc[P + 5];
                 zc[0] = zbefore; zc[1] = zstart;
@@ -1109,10 +1164,14 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
             // consumer block b = positions b * kBlockCols + (LANES - 1) ...: 8 * (LANES - 1) bytes into producer block b
             const u32* const gIn = MULTI ? gBorder + 2 * (LANES - 1) + 4 * lane : nullptr;
             // What lane 0 takes in the FIRST stripe, where no stripe lies above: columns j, j + 1 -> (H, F, H, F) with H the
-            // local-alignment boundary in the column's frame — zero level a * (j mod K + LANES) raised to the class of the lane's
-            // last row, the frame row 0's diagonal term expects (OFFS; plain form: the kind's zero) — and F "no vertical gap"
+            // local-alignment boundary in the frame row 0's diagonal term expects — kUni: the zero level of the step before
+            // (t_g = j - 1) in the class of a lane's last row, a * ((j mod K) + lastClass); column frame: a * (j + LANES +
+            // lastClass); plain form: the kind's zero — and F "no vertical gap"
             auto first_stripe_pairs = [&](int j) -> uint4 {
-                if constexpr (OFFS) {
+                if constexpr (kUni) {
+                    constexpr int kLastClass = (R - 1) % P;
+                    return make_uint4(A::zero_at(p.gex_mag, (j & kmask) + kLastClass), A::kZero, A::zero_at(p.gex_mag, ((j + 1) & kmask) + kLastClass), A::kZero);
+                } else if constexpr (OFFS) {
                     constexpr int kLastClass = (R - 1) % P;
                     const int K = 4 * rq;   // frame period (0: the frame is never lowered)
                     const int j0 = K > 0 ? (j & (K - 1)) : j, j1 = K > 0 ? ((j + 1) & (K - 1)) : j + 1;
@@ -1166,29 +1225,32 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
                 nxt = *reinterpret_cast<const uint2*>(inPtr);   // what the last step prefetched was the old block's
             };
 
-            auto quad = [&](int q, auto lower_tag) {
-                constexpr bool LOWER = decltype(lower_tag)::value;
+            // kUni: every lane lowers its frame by a*K after the last step of a frame period (u = K - 1) — H, E, the values in
+            // flight to the next lane and the next step (Hlast, Fout, upH_prev) and the running maxima — BEFORE the last lane
+            // stores its pair into the OUT ring, so that the next stripe's lane 0, one step later, reads it in its own frame
+            auto lower_frame = [&]() {
+                if constexpr (kUni) {
+                    const u32 w = p.renorm_word;
+#pragma unroll
+                    for (int r = 0; r < R; r++) { st.H[r] = A::lower(st.H[r], w); st.E[r] = A::lower(st.E[r], w); }
+                    st.upH_prev = A::lower(st.upH_prev, w);
+                    // int16: lane 0's diagonal may be a border ring's "no value" (the bias, level 0), which a*K > 1024 takes
+                    // below 0 and the next diagonal addition would wrap into the NaN patterns.  Every real value it can
+                    // hold lies at or above level - a (the boundary at lastClass 0): the floor keeps "no value" below them.
+                    if constexpr (KIND == I16X2) st.upH_prev = A::true_max(st.upH_prev, A::gap(A::kZero, p.gex));
+                    st.Hlast = A::lower(st.Hlast, w);
+                    st.Fout = A::lower(st.Fout, w);
+#pragma unroll
+                    for (int d = 0; d < P + 3; d++) st.maxv[d] = A::lower(st.maxv[d], w);
+                }
+            };
+            auto quad = [&](int q) {
                 if ((q & (kQuadsPerLetterBlock - 1)) == 0) {
                     lettersA = nextA; lettersB = nextB;
                     nextA = fetch(s0, len0pad, q / kQuadsPerLetterBlock + 1);
                     if constexpr (A::kPacked) nextB = fetch(s1, len1pad, q / kQuadsPerLetterBlock + 1);
                 }
-                // OFFS on long subjects: the frame of column j is a*(j mod K + LANES), i.e. a lane lowers everything it
-                // holds by a*K right before it enters a column that is a multiple of K (lane l at step m*K + l).  The
-                // values it receives for that column come from a lane that has already done so, the ones it passed
-                // on last belong to the column before: the frame stays a function of the column alone, which is what
-                // keeps the stripe borders consistent.  16 of K steps pay 2R + 4 extra instructions.
-                const int lower_lane = 4 * (q & (rq - 1));
-                auto lower_frame = [&](int k) {
-                    const u32 gw = lane == k ? p.renorm_word : 0u;
-#pragma unroll
-                    for (int r = 0; r < R; r++) { st.H[r] = A::gap(st.H[r], gw); st.E[r] = A::gap(st.E[r], gw); }
-                    st.upH_prev = A::gap(st.upH_prev, gw);
-#pragma unroll
-                    for (int k = 0; k < P + 4; k++) st.Zc[k] = A::gap(st.Zc[k], gw);
-#pragma unroll
-                    for (int d = 0; d < P + 3; d++) st.maxv[d] = A::gap(st.maxv[d], gw);
-                };
+                const bool lower = kUni && ((tg0 + 4 * q + 4) & kmask) == 0;   // wave-uniform
                 // one step: lane 0's pair of the stripe above from the IN ring, the last lane's own pair into the OUT ring.
                 // The pair is requested ONE STEP AHEAD (nxt): the chain of a step starts with it (row 0's diagonal and F),
                 // and an LDS read issued at the top of the step would be waited for right there.
@@ -1203,56 +1265,37 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
                             nxt = *reinterpret_cast<const uint2*>(inPtr + 8 * (BYTE + 1));
                         }
                     }
-                    dp_step<KIND, R, LANES, BYTE, MULTI, OFFS, P>(st, lds, lettersA, lettersB, p.gop, p.gex, in.x, in.y, apos, first, p.wrap_class, p.wrap_last, head, laneStep);
+                    dp_step<KIND, R, LANES, BYTE, MULTI, OFFS, P, true, kUni>(st, lds, lettersA, lettersB, p.gop, p.gex, in.x, in.y, apos, first,
+                                                                          p.wrap_class, p.wrap_last, head, laneStep, zw);
+                    if constexpr (kUni && BYTE == 3) {
+                        if (lower) lower_frame();
+                    }
                     if constexpr (MULTI) *reinterpret_cast<uint2*>(outPtr + 8 * BYTE) = make_uint2(st.Hlast, st.Fout);
                 };
-                if constexpr (LOWER) lower_frame(lower_lane + 0);
                 border_step(std::integral_constant<int, 0>{});
-                if constexpr (LOWER) lower_frame(lower_lane + 1);
                 border_step(std::integral_constant<int, 1>{});
-                if constexpr (LOWER) lower_frame(lower_lane + 2);
                 border_step(std::integral_constant<int, 2>{});
-                if constexpr (LOWER) lower_frame(lower_lane + 3);
                 border_step(std::integral_constant<int, 3>{});
                 if constexpr (MULTI) outPtr += walkOut;
                 lettersA = dpp<SHL1, true>(0u, lettersA);
                 if constexpr (A::kPacked) lettersB = dpp<SHL1, true>(0u, lettersB);
-                if constexpr (OFFS && A::kWindow) {  // the windows move on by four columns
+                if constexpr (OFFS && A::kWindow) {  // the windows move on by four columns (kUni: steps; its levels are scalar)
+                    if constexpr (!kUni) {
 #pragma unroll
-                    for (int k = 0; k < P + 4; k++) st.Zc[k] = A::add(st.Zc[k], apos4);
+                        for (int k = 0; k < P + 4; k++) st.Zc[k] = A::add(st.Zc[k], apos4);
+                    }
 #pragma unroll
                     for (int d = 0; d < P + 3; d++) st.maxv[d] = A::add(st.maxv[d], apos4);
                 }
+                if constexpr (kUni) load_levels(q + 1);
             };
-            // the quads in which lanes lower their frame (the first LANES/4 of every K/4 quads but the first) run a second
-            // copy of the loop body, so that the others pay nothing for it
             if constexpr (!MULTI) {
-                const int seg = (kLowers && rq > 0) ? rq : nquads;
-                for (int q0 = 0; q0 < nquads; q0 += seg) {
-                    const int qend = min(nquads, q0 + seg);
-                    int q = q0;
-                    if constexpr (kLowers) {
-                        if (q0 > 0) {
-                            const int qlow = min(qend, q0 + LANES / 4);
-                            for (; q < qlow; q++) quad(q, std::true_type{});
-                        }
-                    }
-                    for (; q < qend; q++) quad(q, std::false_type{});
-                }
+                for (int q = 0; q < nquads; q++) quad(q);
             } else {
-                // multi-stripe: block by block (Border<LANES>: kQuadsPerBlock quads, then the block transfer); the lowering
-                // period K/4 is a multiple of the block and the LANES/4 lowering quads fit in one
-                static_assert(BD::kQuadsPerBlock >= LANES / 4, "the lowering quads of a period must lie in one block");
+                // multi-stripe: block by block (Border<LANES>: kQuadsPerBlock quads, then the block transfer)
                 for (int q0 = 0; q0 < nquads; q0 += BD::kQuadsPerBlock) {
                     const int qend = min(nquads, q0 + BD::kQuadsPerBlock);
-                    int q = q0;
-                    if constexpr (kLowers) {
-                        if (rq > 0 && q0 > 0 && (q0 & (rq - 1)) == 0) {
-                            const int qlow = min(qend, q0 + LANES / 4);
-                            for (; q < qlow; q++) quad(q, std::true_type{});
-                        }
-                    }
-                    for (; q < qend; q++) quad(q, std::false_type{});
+                    for (int q = q0; q < qend; q++) quad(q);
                     if (qend == q0 + BD::kQuadsPerBlock) block_end(q0 / BD::kQuadsPerBlock);
                 }
             }
@@ -1272,7 +1315,12 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
                     *reinterpret_cast<uint4*>(g + 4 * lane) = *reinterpret_cast<const uint4*>(ringOut + 16 * lane);
                 }
             }
-            if constexpr (OFFS) {
+            if constexpr (kUni) {
+                // accumulator d and zero level zw[d + 1] (the window of quad nquads) are in the same frame -> true scores
+                maxv = A::true_of(st.maxv[0], zw[1]);
+#pragma unroll
+                for (int d = 1; d < P + 3; d++) maxv = A::true_max(maxv, A::true_of(st.maxv[d], zw[d + 1]));
+            } else if constexpr (OFFS) {
                 if constexpr (A::kWindow) {
                     // accumulator d and zero level d are in the same frame -> true scores
                     maxv = A::true_of(st.maxv[0], st.Zc[0]);
@@ -1310,8 +1358,18 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
             }
             sc0 = A::true_lo(maxv);
             sc1 = A::true_hi(maxv);
-            // no value of the alignment exceeded score + a * (columns + LANES): inside the exact range below the limit
-            guard = p.gex_mag * ((rq > 0 && 4 * nquads > 4 * rq ? 4 * rq : 4 * nquads) + 2 * LANES + 4 + P);
+            // no value of the alignment exceeded score + its cell's zero level: inside the exact range below the limit.  Column
+            // frame: a * (columns + 2 LANES + ...); uniform frame: a * (t_g + P + ...), t_g < 4 nquads + LANES (nstripes - 1) or K
+            if constexpr (kUni) {
+                // (and never less than the column frame would: the same subjects are flagged and re-scored wherever that
+                // bound is the larger one — in practice everywhere but short subjects of queries of many stripes)
+                const int tgmax = 4 * nquads + LANES * (p.nstripes - 1);
+                constexpr int kColP = frame_classes(true, R, LANES, MULTI);
+                guard = max(p.gex_mag * ((tgmax > 4 * rq ? 4 * rq : tgmax) + P + 8),
+                            p.gex_mag * (min(4 * nquads, p.flag_period) + 2 * LANES + 4 + kColP));
+            } else {
+                guard = p.gex_mag * (4 * nquads + 2 * LANES + 4 + P);
+            }
         } else {
             maxv = group_max<KIND, LANES>(maxv);
             sc0 = A::score_lo(maxv);
@@ -1346,7 +1404,7 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
 template <int KIND, int R, int LANES>
 __global__ void sw_build_profile_kernel(const int8_t* __restrict__ query, int32_t qlen,
                                         const int8_t* __restrict__ matrix21, int32_t pad_row, int32_t nstripes,
-                                        unsigned char* __restrict__ profile, int32_t shift) {
+                                        unsigned char* __restrict__ profile, int32_t shift, int32_t head_extra) {
     using A = Arith<KIND>;
     using G = Geometry<KIND, R, LANES>;
     constexpr int kWordsPerRow = G::kRowBytes / 4;
@@ -1367,10 +1425,12 @@ __global__ void sw_build_profile_kernel(const int8_t* __restrict__ query, int32_
                 // matrix21: (query letters + one padding row `pad_row`) x 21 subject letters
                 const int qc = row < qlen ? (int)query[row] : pad_row;
                 // OFFS kernels (shift = a): the diagonal step raises the frame by a per column and by a per row class;
-                // the row above lane-local row 0 is the previous lane's last row (dp_step<OFFS>)
-                const int P = frame_classes(A::kPacked, R, LANES, nstripes > 1);  // the scan kernel's (MULTI == more than one stripe)
+                // the row above lane-local row 0 is the previous lane's last row (dp_step<OFFS>), whose frame lies a further
+                // a * head_extra below in the uniform frame (sw_scan_kernel; head_extra = 1; the column frame: 0)
+                const int P = frame_classes(A::kPacked, R, LANES, nstripes > 1, head_extra != 0);  // the scan kernel's (MULTI == more than one stripe)
                 const int cls = row_in_lane % P, above = (row_in_lane == 0 ? R - 1 : row_in_lane - 1) % P;
-                return A::encode_score((int)matrix21[qc * kLetters + letter] + shift * (1 + cls - above));
+                const int head = row_in_lane == 0 ? head_extra : 0;
+                return A::encode_score((int)matrix21[qc * kLetters + letter] + shift * (1 + head + cls - above));
             };
             if constexpr (G::kWide) v = w < R ? (entry(w) | (A::kOne << 16)) : 0u;
             else if constexpr (A::kPacked) v = entry(2 * w) | (entry(2 * w + 1) << 16);

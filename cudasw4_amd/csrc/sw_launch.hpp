@@ -48,8 +48,9 @@ struct KindLaunch {
     // reserve > 0: the grid is capped at the workgroups the device holds of this kernel at once, minus `reserve` (slots left
     // free for small launches of other streams while the persistent grid runs: sw_set_grid_reserve)
     hipError_t (*scan)(int R, int lanes, bool multi, bool offs, int grid, int reserve, hipStream_t stream, const ScanParams& p);
+    // head_extra: 1 for the uniform frame of the packed sw_scan_kernel (uniform_frame_launch), else 0
     hipError_t (*profile)(int R, int lanes, const int8_t* query, int32_t qlen, const int8_t* matrix21, int32_t pad_row,
-                          int32_t nstripes, unsigned char* out, int32_t shift, hipStream_t stream);
+                          int32_t nstripes, unsigned char* out, int32_t shift, int32_t head_extra, hipStream_t stream);
     size_t (*tile_bytes)(int R, int lanes);
     // an empty launch from the kind's translation unit: the runtime loads a TU's code object (a few MB of kernels) on
     // the first launch of any of its kernels; sw_ctx_create pays that once instead of the first query (~25 ms per kind)
@@ -108,6 +109,12 @@ hipError_t launch_scan_k(K kernel, int grid, int reserve, hipStream_t stream, co
 //     multi-stripe launches whose subjects are short enough for rounds of several slots to pay; sw_scan_kernel for the other
 //     multi-stripe launches;
 //   * 8- and 4-lane groups: single-stripe kernels only (queries of up to 256 / 128 residues).
+// Which launches run the uniform frame (sw_scan_kernel: the packed kinds' column-offset recurrence) and need its profile and
+// ScanParams::levels; the streamed kernels keep the column frame with per-lane zero levels.  Must match launch_scan_ro.
+constexpr bool uniform_frame_launch(bool packed, bool offs, int lanes, bool multi, int stream_slots) {
+    return packed && offs && !(lanes == 16 && (!multi || stream_slots > 1));
+}
+
 template <int KIND, int R, int LANES, bool OFFS>
 hipError_t launch_scan_ro(bool multi, int grid, int reserve, hipStream_t stream, const ScanParams& p) {
     // a query that needs more than one stripe always gets R > max/2 from the planner
@@ -115,6 +122,9 @@ hipError_t launch_scan_ro(bool multi, int grid, int reserve, hipStream_t stream,
     constexpr bool kPacked = Arith<KIND>::kPacked;
     if constexpr (R > kMaxR || (kPacked && !OFFS)) {
         return hipErrorInvalidValue;
+    } else if ((p.uniform_frame != 0) != uniform_frame_launch(kPacked, OFFS, LANES, multi, p.stream_slots) ||
+               (p.uniform_frame && (p.renorm_quads < LANES || 4 * p.renorm_quads > kUniformMaxPeriod))) {
+        return hipErrorInvalidValue;   // a profile / level table of the other frame
     } else if constexpr (kPacked && LANES == 16) {
         if (p.positions || p.claim || p.service || p.count_ptr || p.stream_slots < 1) return hipErrorInvalidValue;   // (32-bit kinds' business)
         if (multi) {
@@ -151,14 +161,14 @@ hipError_t launch_scan_r(bool multi, bool offs, int grid, int reserve, hipStream
 
 template <int KIND, int R, int LANES>
 hipError_t launch_profile_r(const int8_t* query, int32_t qlen, const int8_t* matrix21, int32_t pad_row, int32_t nstripes,
-                            unsigned char* out, int32_t shift, hipStream_t stream) {
+                            unsigned char* out, int32_t shift, int32_t head_extra, hipStream_t stream) {
     if constexpr (R > max_rows(KIND, LANES)) {
         return hipErrorInvalidValue;
     } else {
         const size_t total = (size_t)nstripes * kLetters * (Geometry<KIND, R, LANES>::kRowBytes / 4);
         const int grid = (int)std::min<size_t>((total + 255) / 256, 65536);  // grid-stride loop covers the rest
         hipLaunchKernelGGL((sw_build_profile_kernel<KIND, R, LANES>), dim3(grid), dim3(256), 0, stream, query, qlen,
-                           matrix21, pad_row, nstripes, out, shift);
+                           matrix21, pad_row, nstripes, out, shift, head_extra);
         return hipGetLastError();
     }
 }
@@ -185,7 +195,7 @@ constexpr size_t tile_bytes_r() {
         return hipErrorInvalidValue;                                                                                \
     }                                                                                                               \
     static hipError_t FN##_profile(int R, int lanes, const int8_t* q, int32_t qlen, const int8_t* m, int32_t pr,    \
-                                   int32_t ns, unsigned char* out, int32_t shift, hipStream_t s) {                  \
+                                   int32_t ns, unsigned char* out, int32_t shift, int32_t hx, hipStream_t s) {      \
         if (lanes == 16) { switch (R) { FOR_EACH_R(SWK_CASE_PROF16_##KIND) } }                                      \
         else if (lanes == 64) { switch (R) { FOR_EACH_R(SWK_CASE_PROF64_##KIND) } }                                 \
         else if (lanes == 8) { switch (R) { FOR_EACH_R(SWK_CASE_PROF8_##KIND) } }                                   \
