@@ -33,6 +33,8 @@ EXPORTS = ["sw_batch_create", "sw_batch_destroy", "sw_scan_batch", "sw_batch_joi
            "sw_scan_rows_pipelined_temp_bytes", "sw_probe_handshake", "sw_launch_vgpr_slot",
            "sw_set_rows_pipeline_slot", "sw_rescore_overflow_pipelined", "sw_rescore_overflow_pipelined_temp_bytes", "sw_measure_valu_rate",
            "sw_align_hits"]
+# ... and include/cudasw4_amd_pssm.h (profile search: a position-specific scoring matrix as the query)
+PSSM_EXPORTS = ["sw_set_query_pssm", "sw_query_is_pssm"]
 
 
 # sw_align_hits (include/cudasw4_amd.h): result records, statuses, flags, CIGAR op codes
@@ -128,6 +130,9 @@ def _load():
                                  ctypes.POINTER(i32), ctypes.POINTER(i32)]
     if hasattr(L, "sw_align_hits"):   # (CUDASW4_AMD_LIB may name an older build)
         L.sw_align_hits.argtypes = [vp, ctypes.POINTER(_AlignArgs)]
+    if hasattr(L, "sw_set_query_pssm"):
+        L.sw_set_query_pssm.argtypes = [vp, vp, i32, vp]
+        L.sw_query_is_pssm.argtypes = [vp]
     return L
 
 
@@ -183,6 +188,18 @@ class Context:
         import numpy as np
         q = np.ascontiguousarray(codes, dtype=np.int8)
         check(lib.sw_set_query(self.handle, q.ctypes.data, len(q), stream))
+
+    def set_query_pssm(self, pssm, stream=0):
+        """Install a position-specific scoring matrix (qlen x 21 int8, column 20 negative) as the query: every scan scores
+        position i against subject code c with pssm[i][c] until the next set_query / set_query_pssm (cudasw4_amd_pssm.h)."""
+        from . import pssm as _pssm
+        if not hasattr(lib, "sw_set_query_pssm"):
+            raise SwError(-1, "this build of libcudasw4_amd.so has no sw_set_query_pssm")
+        m = _pssm.as_pssm(pssm)
+        check(lib.sw_set_query_pssm(self.handle, m.ctypes.data, m.shape[0], stream))
+
+    def query_is_pssm(self):
+        return bool(lib.sw_query_is_pssm(self.handle))
 
     def scan_temp_bytes(self, kind, part_id, n, max_subject_len):
         return int(lib.sw_scan_temp_bytes(self.handle, kind, part_id, n, max_subject_len))

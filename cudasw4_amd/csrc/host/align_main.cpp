@@ -17,6 +17,7 @@
 #include "cli_options.hpp"
 #include "db_format.hpp"
 #include "hit_alignment.hpp"
+#include "pssm_query.hpp"
 #include "search_driver.hpp"
 #include "sequence_reader.hpp"
 
@@ -150,6 +151,27 @@ void processQueryFile(const std::string& file, const ProgramOptions& o, SearchDr
     }
 }
 
+// One --pssm file: a single query (number 0 of its "file"), printed like a query of a query file; header = the file's base name
+void processPssmQuery(const PssmQuery& q, const ProgramOptions& o, SearchDriver& driver, std::ostream& out) {
+    driver.totalTimerStart();
+    std::cout << "Processing query " << 0 << " ... ";
+    std::cout.flush();
+    submit_pssm(driver, q.scores.data(), q.length());
+    ScanResult r = driver.collect();
+    reportScan(o, r);
+    if (o.numTopOutputs > 0) {
+        if (o.outputMode == ProgramOptions::OutputMode::Plain) {
+            out << "Query " << 0 << ", header " << q.name << ", length " << q.length() << ", num overflows " << r.stats.numOverflows << "\n";
+            printScanResultPlain(out, r, driver);
+        } else {
+            printScanResultTSV(out, r, driver, 0, int64_t(q.length()), q.name);
+        }
+        out.flush();
+    }
+    const BenchmarkStats total = driver.totalTimerStop();
+    if (o.verbose) std::cout << "Total time: " << total.seconds << " s, " << total.gcups << " GCUPS\n";
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -161,6 +183,13 @@ int main(int argc, char** argv) {
     }
     printOptions(options);
     try {
+        // PSSM queries are read and validated before any device is opened: a malformed file is an error of the command line
+        if (!options.pssmFiles.empty() && options.alignments)
+            throw std::runtime_error("--pssm cannot be combined with --alignments: hit alignment of PSSM queries is not supported");
+        if (!options.pssmFiles.empty() && options.interactive)
+            throw std::runtime_error("--pssm cannot be combined with --interactive");
+        std::vector<PssmQuery> pssmQueries;
+        for (const auto& file : options.pssmFiles) pssmQueries.push_back(read_ascii_pssm(file));
         std::vector<int> deviceIds;
         int num = 0;
         if (hipGetDeviceCount(&num) != hipSuccess) num = 0;
@@ -209,9 +238,11 @@ int main(int argc, char** argv) {
         if (options.alignments) aligner = std::make_unique<HitAligner>(driver);
 
         if (!options.interactive) {
-            for (const auto& queryFile : options.queryFiles) {
-                std::cout << "Processing query file " << queryFile << "\n";
-                processQueryFile(queryFile, options, driver, outputfile, false, aligner.get());
+            size_t nextPssm = 0;
+            for (const auto& input : options.inputs) {
+                std::cout << "Processing query file " << input.path << "\n";
+                if (input.pssm) processPssmQuery(pssmQueries[nextPssm++], options, driver, outputfile);
+                else processQueryFile(input.path, options, driver, outputfile, false, aligner.get());
             }
         } else {
             // main.cu:336-424

@@ -32,6 +32,7 @@ void printOptions(const ProgramOptions& o) {
     std::cout << "maxBatchSequences: " << o.memory.maxBatchSequences << "\n";
     std::cout << "maxTempBytes: " << o.memory.maxTempBytes << "\n";
     for (size_t i = 0; i < o.queryFiles.size(); i++) std::cout << "queryFile " << i << " : " << o.queryFiles[i] << "\n";
+    for (size_t i = 0; i < o.pssmFiles.size(); i++) std::cout << "pssmFile " << i << " : " << o.pssmFiles[i] << "\n";
     std::cout << "blosum: " << substitution_matrix(o.matrix).name << "\n";
     std::cout << "singlePassType: " << to_string(o.kernels.singlePassType) << "\n";
     std::cout << "manyPassType_small: " << to_string(o.kernels.manyPassType_small) << "\n";
@@ -52,6 +53,8 @@ void printOptions(const ProgramOptions& o) {
 bool parseArgs(int argc, char** argv, ProgramOptions& o) {
     bool gotQuery = false, gotDB = false, gotGex = false, gotGop = false, gotDPX = false;
     o.queryFiles.clear();
+    o.pssmFiles.clear();
+    o.inputs.clear();
     auto value = [&](int& i) -> std::string {
         if (i + 1 >= argc) { std::cout << "Missing value for " << argv[i] << "\n"; return std::string(); }
         return argv[++i];
@@ -76,7 +79,8 @@ bool parseArgs(int argc, char** argv, ProgramOptions& o) {
         else if (arg == "--maxBatchSequences") o.memory.maxBatchSequences = size_t(std::atoll(value(i).c_str()));
         else if (arg == "--maxTempBytes") o.memory.maxTempBytes = parseMemoryString(value(i));
         else if (arg == "--maxGpuMem") o.memory.maxGpuMem = parseMemoryString(value(i));
-        else if (arg == "--query") { o.queryFiles.push_back(value(i)); gotQuery = true; }
+        else if (arg == "--query") { o.queryFiles.push_back(value(i)); o.inputs.push_back({o.queryFiles.back(), false}); gotQuery = true; }
+        else if (arg == "--pssm") { o.pssmFiles.push_back(value(i)); o.inputs.push_back({o.pssmFiles.back(), true}); gotQuery = true; }
         else if (arg == "--db") { o.dbPrefix = value(i); gotDB = true; }
         else if (arg == "--mat") {
             const std::string v = value(i);
@@ -122,6 +126,8 @@ void printHelp(char** argv) {
     std::cout << "Options: \n";
     std::cout << "   Mandatory\n";
     std::cout << "      --query queryfile : Mandatory. Fasta or Fastq. Can be gzip'ed. Repeat this option for multiple query files\n";
+    std::cout << "      --pssm pssmfile : A position-specific scoring matrix as a query, in place of or beside --query: an NCBI ASCII PSSM\n"
+                 "        (psiblast -out_ascii_pssm). Repeat this option for multiple PSSMs. Not with --alignments\n";
     std::cout << "      --db dbPrefix : Mandatory. The DB to query against. The same dbPrefix as used for makedb\n\n";
     std::cout << "   Scoring\n";
     std::cout << "      --top val : Output the val best scores. Default val = " << d.numTopOutputs << "\n";

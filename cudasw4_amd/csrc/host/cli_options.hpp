@@ -42,6 +42,10 @@ struct ProgramOptions {
     std::string outputfile = "/dev/stdout";
     std::string dbPrefix;
     std::vector<std::string> queryFiles;
+    // --pssm: NCBI ASCII PSSM files, each one query (pssm_query.hpp); `inputs` keeps --query and --pssm in the order given
+    std::vector<std::string> pssmFiles;
+    struct QueryInput { std::string path; bool pssm; };
+    std::vector<QueryInput> inputs;
 };
 
 void printOptions(const ProgramOptions& options);

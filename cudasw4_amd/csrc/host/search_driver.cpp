@@ -1182,7 +1182,8 @@ void SearchDriver::enqueueOnGpu(Gpu& g, int32_t queryLength, int k, int slot, bo
         if (g.badCodes) throw DbLoadError("DB chars hold letter codes outside 0..20 (not a cudasw4 DB, or corrupt)");
         g.qlen = queryLength;
         if (!g.cacheFilled) uploadShard(g);  // the first query pays the upload unless --uploadFull
-        SWCHECK(sw_set_query(g.ctx, encodedQuery_.data(), queryLength, g.stream));
+        if (queryInstall_) SWCHECK(queryInstall_(g.ctx, encodedQuery_.data(), queryLength, g.stream));
+        else SWCHECK(sw_set_query(g.ctx, encodedQuery_.data(), queryLength, g.stream));
         // thrust::fill(scores, -1) (cudasw4.cuh:405-409) is not needed: every slot is written by a scan or a re-score
         // + 1: the bad-letter flag of streamed batches that are checked on the device (scanStreamed); + 1: pipeline stages
         // that gave up waiting (sw_scan_rows_pipelined: fail_count)
@@ -1370,16 +1371,35 @@ void SearchDriver::finishOnGpu(Gpu& g, int slot, int32_t qlen) {
     g.spanEnd = now_seconds() - scanT0_;
 }
 
-void SearchDriver::submit(const char* query, int32_t queryLength) {
-    if (!db_) throw std::runtime_error("setDatabase first");
+namespace {
+void check_submit(const void* db, int32_t queryLength, size_t pending) {
+    if (!db) throw std::runtime_error("setDatabase first");
     if (queryLength <= 0) throw std::runtime_error("empty query");
     if (queryLength > INT32_MAX - 132) throw std::runtime_error("query too long");  // cudasw4.cuh:1281-1285
-    if (pendingCount_ >= size_t(kMaxInFlight)) throw std::runtime_error("too many queries in flight: collect() first");
+    if (pending >= size_t(SearchDriver::kMaxInFlight)) throw std::runtime_error("too many queries in flight: collect() first");
+}
+}  // namespace
+
+void SearchDriver::submitWith(QueryInstallFn install, const int8_t* data, size_t bytes, int32_t queryLength) {
+    check_submit(db_.get(), queryLength, pendingCount_);
+    if (!install || !data) throw std::runtime_error("submitWith: null argument");
+    encodedQuery_.assign(data, data + bytes);
+    queryInstall_ = install;
+    submitEncoded(queryLength);
+}
+
+void SearchDriver::submit(const char* query, int32_t queryLength) {
+    check_submit(db_.get(), queryLength, pendingCount_);
     encodedQuery_.resize(size_t(queryLength));
     // 25-letter tables: the query keeps B, J, Z, X and '*' apart; the DB side stays the dbdata alphabet (include/cudasw4_amd.h)
     if (matrix_.dim == 25) for (int32_t i = 0; i < queryLength; i++) encodedQuery_[size_t(i)] = encode_residue25(query[i]);
     else for (int32_t i = 0; i < queryLength; i++) encodedQuery_[size_t(i)] = encode_residue(query[i]);
+    queryInstall_ = nullptr;
+    submitEncoded(queryLength);
+}
 
+// the query is in encodedQuery_ (letters, or what queryInstall_ takes): enqueue it on every GPU
+void SearchDriver::submitEncoded(int32_t queryLength) {
     TraceRange traceQuery("submit query of %d residues (%d in flight)", int(queryLength), int(pendingCount_));
     PendingScan ps;
     ps.slot = nextSlot_;

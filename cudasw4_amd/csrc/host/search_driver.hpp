@@ -188,6 +188,12 @@ public:
     // queries of one driver still run one after the other on each GPU.
     static constexpr int kMaxInFlight = 4;
     void submit(const char* query, int32_t queryLength);
+    // A query that is not a residue string (pssm_query.cpp: a position-specific scoring matrix): `data` (`bytes` of it, copied)
+    // is handed to `install` on every GPU in place of the encoded letters and sw_set_query; everything behind the install
+    // — shards, residency, streaming, lanes, merge, collect() — is that of a letter query of queryLength residues.  The
+    // function lives in the caller's translation unit, so this file needs no entry point of the library beyond the boundary.
+    using QueryInstallFn = int (*)(sw_ctx* ctx, const int8_t* data, int32_t queryLength, void* stream);
+    void submitWith(QueryInstallFn install, const int8_t* data, size_t bytes, int32_t queryLength);
     ScanResult collect();
     int inFlight() const { return int(pendingCount_); }
 
@@ -256,6 +262,7 @@ private:
     struct Worker;
     void uploadShard(Gpu& g);
     void scanStreamed(Gpu& g);
+    void submitEncoded(int32_t queryLength);
     void enqueueOnGpu(Gpu& g, int32_t queryLength, int k, int slot, bool inFlight);
     bool prepareLane(Gpu& g, int32_t queryLength);
     bool laneEligible(const Gpu& g, int32_t queryLength) const;
@@ -279,6 +286,7 @@ private:
     bool dbRegistered_ = false;  // the streamed ranges of the DB's chars mapping are registered with the runtime (direct DMA)
     std::vector<std::pair<const int8_t*, size_t>> registered_;  // what hipHostRegister was given
     std::vector<int8_t> encodedQuery_;
+    QueryInstallFn queryInstall_ = nullptr;   // submitWith: what installs encodedQuery_ (nullptr: sw_set_query)
     double scanT0_ = 0;
     double watchdogSeconds_ = 60.0;   // CUDASW4_AMD_WATCHDOG_SECONDS: base of collect()'s deadline (0: none)
     // queries submitted and not yet collected, oldest first (a ring of kMaxInFlight result slots per GPU)

@@ -17,8 +17,10 @@
 
 #include "../../include/cudasw4_amd.h"
 #include "../../include/cudasw4_amd_engine.h"
+#include "../../include/cudasw4_amd_pssm.h"
 #include "sw_internal.hpp"
 #include "sw_launch.hpp"
+#include "sw_pssm.hpp"
 #include "sw_rows_pipeline.hpp"
 
 namespace {
@@ -171,6 +173,12 @@ struct sw_ctx {
     int query_next = 0;
     int32_t qlen = 0;
     bool have_query = false;
+    // sw_set_query_pssm: the query is a position-specific scoring matrix, staged on the device in the tiled form of
+    // sw_pssm.hpp; d_query and the matrix are not read while it is installed
+    bool pssm_mode = false;
+    int8_t* d_pssm = nullptr;
+    size_t pssm_capacity = 0;
+    int pssm_max = 1;            // largest entry of the installed PSSM: what matrix_max is to a letter query
     Profile profiles[4][4][3];  // [kind][shape: 0 = 16-lane groups, 1 = 64-lane groups, 2 = 8-lane groups, 3 = 4-lane groups][plain | column frame | uniform frame]
     bool use_offs = true;        // CUDASW4_AMD_NO_OFFS=1: always the plain recurrence (A/B measurements)
     int64_t long16_min = -1;     // sw_set_long16_min: partition 34 gets 16-lane groups from this many subjects up (-1: 512)
@@ -194,6 +202,13 @@ struct sw_ctx {
 };
 
 namespace {
+
+// The largest score one aligned pair of residues can add: every bound that is derived from "a score cannot exceed
+// (aligned columns) x (largest substitution score)" reads it here, so that a PSSM query is bounded by its own entries
+// and not by a table it never uses.
+int score_max(const sw_ctx* ctx) { return std::max(1, ctx->pssm_mode ? ctx->pssm_max : ctx->matrix_max); }
+// something to score with: a substitution table for a letter query; a PSSM query brings its own scores
+bool have_scores(const sw_ctx* ctx) { return ctx->have_matrix || ctx->pssm_mode; }
 
 int max_grid(const sw_ctx* ctx) {
     const int g = std::max(1, ctx->num_cus) * ctx->grid_mult;
@@ -221,7 +236,7 @@ int shape_index(int lanes) { return lanes == 64 ? 1 : lanes == 8 ? 2 : lanes == 
 // of the same size, gets the true int32 kernels.
 int effective_kind_of(const sw_ctx* ctx, int kind, int32_t max_subject_len) {
     if (kind != SW_KIND_I32 || ctx->i32_native || !ctx->have_query) return kind;
-    const int64_t bound = (int64_t)std::min(ctx->qlen, max_subject_len) * std::max(1, ctx->matrix_max) + ((int64_t)1 << 22) + 4096;
+    const int64_t bound = (int64_t)std::min(ctx->qlen, max_subject_len) * score_max(ctx) + ((int64_t)1 << 22) + 4096;
     return bound < ((int64_t)1 << 24) ? SW_KIND_F32 : SW_KIND_I32;
 }
 
@@ -284,7 +299,9 @@ int ensure_profile(sw_ctx* ctx, int kind, int lanes, int frame, int shift, hipSt
         SW_HIP(hipMalloc(&pr.dev, cap));
         pr.capacity = cap;
     }
-    SW_HIP(kl->profile(pl.rows, lanes, ctx->d_query, ctx->qlen, ctx->d_matrix, ctx->dim, pl.nstripes, pr.dev, shift, frame == 2 ? 1 : 0, stream));
+    // (a null query selects the builder's PSSM source: scores by query position from the staged PSSM, padding row = qlen)
+    if (ctx->pssm_mode) SW_HIP(kl->profile(pl.rows, lanes, nullptr, ctx->qlen, ctx->d_pssm, ctx->qlen, pl.nstripes, pr.dev, shift, frame == 2 ? 1 : 0, stream));
+    else SW_HIP(kl->profile(pl.rows, lanes, ctx->d_query, ctx->qlen, ctx->d_matrix, ctx->dim, pl.nstripes, pr.dev, shift, frame == 2 ? 1 : 0, stream));
     pr.shift = shift;
     if (!pr.ready) SW_HIP(hipEventCreateWithFlags(&pr.ready, hipEventDisableTiming));
     SW_HIP(hipEventRecord(pr.ready, stream));
@@ -417,7 +434,7 @@ int scan_common(sw_ctx* ctx, int kind, int lanes, const int8_t* chars, const uin
         return fail(SW_ERR_INVALID, "max_subject_len " + std::to_string(max_subject_len) + ": pass the longest subject of the range (lengths[last]), not the partition's nominal boundary");
     if (gop > 0 || gex > 0) return fail(SW_ERR_INVALID, "gap scores must be <= 0");
     if (kind_packed(kind) && (gop < -1000 || gex < -1000)) return fail(SW_ERR_INVALID, "gap score out of range for a 16-bit kind");
-    if (!ctx->have_matrix) return fail(SW_ERR_NO_MATRIX, "sw_set_matrix has not been called");
+    if (!have_scores(ctx)) return fail(SW_ERR_NO_MATRIX, "sw_set_matrix has not been called");
     if (!ctx->have_query) return fail(SW_ERR_NO_QUERY, "sw_set_query has not been called");
     if (n == 0) return SW_OK;
     if (!chars || !offsets || !lengths || !scores || !ids) return fail(SW_ERR_INVALID, "null buffer");
@@ -636,6 +653,55 @@ const int8_t* matrix(const sw_ctx* ctx, int* dim) {
 }
 }  // namespace swi
 
+namespace {
+// What sw_set_query and sw_set_query_pssm share: `bytes` of query data, written by `fill` into a pinned staging buffer,
+// uploaded stream-ordered into *dev (grown on demand), and the book-keeping of a new query.
+template <class Fill>
+int install_query(sw_ctx* ctx, int8_t** dev, size_t* dev_capacity, size_t bytes, int32_t qlen, bool pssm, void* stream, Fill fill) {
+    SW_HIP(hipSetDevice(ctx->device));
+    if (bytes > *dev_capacity) {
+        if (*dev) SW_HIP(hipFree(*dev));
+        *dev = nullptr;
+        *dev_capacity = 0;
+        const size_t cap = std::max<size_t>((bytes + 4095) / 4096 * 4096 * 2, size_t(1) << 16);
+        SW_HIP(hipMalloc(dev, cap));
+        *dev_capacity = cap;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // Pinned staging ring: the caller's buffer is copied on the host (a few KB) and is free again on return; the upload
+    // itself is stream-ordered — behind the scans of the previous query that still read d_query or its profiles on `s`
+    // — and nothing here waits for the GPU unless the ring has wrapped around onto a copy that is still in flight.
+    const int slot = ctx->query_next;
+    ctx->query_next = (ctx->query_next + 1) % sw_ctx::kQuerySlots;
+    if (ctx->query_slot_used[slot]) SW_HIP(hipEventSynchronize(ctx->query_copied[slot]));
+    if (bytes > ctx->h_query_capacity[slot]) {
+        if (ctx->h_query[slot]) SW_HIP(hipHostFree(ctx->h_query[slot]));
+        ctx->h_query[slot] = nullptr;
+        ctx->h_query_capacity[slot] = 0;
+        const size_t cap = std::max<size_t>((bytes + 4095) / 4096 * 4096 * 2, size_t(1) << 16);
+        SW_HIP(hipHostMalloc(&ctx->h_query[slot], cap));
+        ctx->h_query_capacity[slot] = cap;
+    }
+    if (!ctx->query_copied[slot]) SW_HIP(hipEventCreateWithFlags(&ctx->query_copied[slot], hipEventDisableTiming));
+    fill(ctx->h_query[slot]);
+    SW_HIP(hipMemcpyAsync(*dev, ctx->h_query[slot], bytes, hipMemcpyHostToDevice, s));
+    // the control words of this query's launches, zeroed in one go (take_work_slot)
+    ctx->work_next = (ctx->work_next + kWorkZeroBlock - 1) / kWorkZeroBlock * kWorkZeroBlock;
+    SW_HIP(hipMemsetAsync(ctx->d_work + 2 * (ctx->work_next % kWorkSlots), 0, 2 * kWorkZeroBlock * sizeof(uint32_t), s));
+    ctx->work_zeroed = kWorkZeroBlock;
+    SW_HIP(hipEventRecord(ctx->query_copied[slot], s));
+    ctx->query_slot_used[slot] = true;
+    ctx->qlen = qlen;
+    ctx->have_query = true;
+    ctx->pssm_mode = pssm;
+    // every switch of query — letters or PSSM, either way round — leaves the cached profiles stale
+    for (auto& row : ctx->profiles)
+        for (auto& shape : row)
+            for (auto& pr : shape) pr.valid = false;
+    return SW_OK;
+}
+}  // namespace
+
 extern "C" {
 
 const char* sw_version(void) { return "cudasw4_amd 0.2 (gfx950)"; }
@@ -694,6 +760,7 @@ int sw_ctx_destroy(sw_ctx* ctx) {
     if (ctx->d_zeros) (void)hipFree(ctx->d_zeros);
     if (ctx->d_work) (void)hipFree(ctx->d_work);
     if (ctx->d_query) (void)hipFree(ctx->d_query);
+    if (ctx->d_pssm) (void)hipFree(ctx->d_pssm);
     for (int i = 0; i < sw_ctx::kQuerySlots; i++) {
         if (ctx->h_query[i]) (void)hipHostFree(ctx->h_query[i]);
         if (ctx->query_copied[i]) (void)hipEventDestroy(ctx->query_copied[i]);
@@ -729,7 +796,7 @@ int sw_set_matrix(sw_ctx* ctx, const int8_t* matrix_host, int dim) {
     SW_HIP(hipMemcpy(ctx->d_matrix, m, (size_t)(dim + 1) * swk::kLetters, hipMemcpyHostToDevice));
     ctx->matrix_max = 1;
     for (int i = 0; i < dim * dim; i++) ctx->matrix_max = std::max(ctx->matrix_max, (int)matrix_host[i]);
-    if (ctx->have_query && dim < ctx->dim) ctx->have_query = false;  // the installed query may hold codes of the larger alphabet
+    if (ctx->have_query && !ctx->pssm_mode && dim < ctx->dim) ctx->have_query = false;  // the installed query may hold codes of the larger alphabet
     ctx->dim = dim;
     ctx->have_matrix = true;
     for (auto& row : ctx->profiles)
@@ -743,46 +810,32 @@ int sw_set_query(sw_ctx* ctx, const int8_t* query_codes_host, int32_t qlen, void
     if (qlen <= 0) return fail(SW_ERR_INVALID, "query length must be positive");
     for (int32_t i = 0; i < qlen; i++)
         if (query_codes_host[i] < 0 || query_codes_host[i] >= ctx->dim) return fail(SW_ERR_INVALID, "query code out of range for the installed matrix");
-    SW_HIP(hipSetDevice(ctx->device));
-    if ((size_t)qlen > ctx->query_capacity) {
-        if (ctx->d_query) SW_HIP(hipFree(ctx->d_query));
-        ctx->d_query = nullptr;
-        ctx->query_capacity = 0;
-        const size_t cap = std::max<size_t>(((size_t)qlen + 4095) / 4096 * 4096 * 2, size_t(1) << 16);
-        SW_HIP(hipMalloc(&ctx->d_query, cap));
-        ctx->query_capacity = cap;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // Pinned staging ring: the caller's buffer is copied on the host (a few KB) and is free again on return; the upload
-    // itself is stream-ordered — behind the scans of the previous query that still read d_query or its profiles on `s`
-    // — and nothing here waits for the GPU unless the ring has wrapped around onto a copy that is still in flight.
-    const int slot = ctx->query_next;
-    ctx->query_next = (ctx->query_next + 1) % sw_ctx::kQuerySlots;
-    if (ctx->query_slot_used[slot]) SW_HIP(hipEventSynchronize(ctx->query_copied[slot]));
-    if ((size_t)qlen > ctx->h_query_capacity[slot]) {
-        if (ctx->h_query[slot]) SW_HIP(hipHostFree(ctx->h_query[slot]));
-        ctx->h_query[slot] = nullptr;
-        ctx->h_query_capacity[slot] = 0;
-        const size_t cap = std::max<size_t>(((size_t)qlen + 4095) / 4096 * 4096 * 2, size_t(1) << 16);
-        SW_HIP(hipHostMalloc(&ctx->h_query[slot], cap));
-        ctx->h_query_capacity[slot] = cap;
-    }
-    if (!ctx->query_copied[slot]) SW_HIP(hipEventCreateWithFlags(&ctx->query_copied[slot], hipEventDisableTiming));
-    memcpy(ctx->h_query[slot], query_codes_host, (size_t)qlen);
-    SW_HIP(hipMemcpyAsync(ctx->d_query, ctx->h_query[slot], qlen, hipMemcpyHostToDevice, s));
-    // the control words of this query's launches, zeroed in one go (take_work_slot)
-    ctx->work_next = (ctx->work_next + kWorkZeroBlock - 1) / kWorkZeroBlock * kWorkZeroBlock;
-    SW_HIP(hipMemsetAsync(ctx->d_work + 2 * (ctx->work_next % kWorkSlots), 0, 2 * kWorkZeroBlock * sizeof(uint32_t), s));
-    ctx->work_zeroed = kWorkZeroBlock;
-    SW_HIP(hipEventRecord(ctx->query_copied[slot], s));
-    ctx->query_slot_used[slot] = true;
-    ctx->qlen = qlen;
-    ctx->have_query = true;
-    for (auto& row : ctx->profiles)
-        for (auto& shape : row)
-            for (auto& pr : shape) pr.valid = false;
-    return SW_OK;
+    return install_query(ctx, &ctx->d_query, &ctx->query_capacity, (size_t)qlen, qlen, false, stream,
+                         [&](int8_t* staged) { memcpy(staged, query_codes_host, (size_t)qlen); });
 }
+
+int sw_set_query_pssm(sw_ctx* ctx, const int8_t* pssm_host, int32_t qlen, void* stream) {
+    if (!ctx || !pssm_host) return fail(SW_ERR_INVALID, "null argument");
+    if (qlen <= 0) return fail(SW_ERR_INVALID, "query length must be positive");
+    if (qlen > SW_PSSM_MAX_QUERY_LEN) return fail(SW_ERR_INVALID, "PSSM query longer than SW_PSSM_MAX_QUERY_LEN");
+    int top = 1;
+    for (int32_t i = 0; i < qlen; i++) {
+        const int8_t* row = pssm_host + (size_t)i * swk::kLetters;
+        if (row[swk::kPadLetter] >= 0)
+            return fail(SW_ERR_INVALID, "PSSM row " + std::to_string(i) + ": the score against the padding letter (column 20) must be negative");
+        for (int j = 0; j < swk::kLetters; j++) top = std::max(top, (int)row[j]);
+    }
+    const int64_t rows = swk::pssm_staged_rows(qlen);
+    const int rc = install_query(ctx, &ctx->d_pssm, &ctx->pssm_capacity, (size_t)rows * swk::kPssmTileLetters, qlen, true, stream, [&](int8_t* staged) {
+        memset(staged, (unsigned char)(int8_t)swk::kPssmPadScore, (size_t)rows * swk::kPssmTileLetters);
+        for (int32_t i = 0; i < qlen; i++)
+            for (int j = 0; j < swk::kLetters; j++) staged[swk::pssm_index(i, j)] = pssm_host[(size_t)i * swk::kLetters + j];
+    });
+    if (rc == SW_OK) ctx->pssm_max = top;
+    return rc;
+}
+
+int sw_query_is_pssm(const sw_ctx* ctx) { return ctx && ctx->have_query && ctx->pssm_mode ? 1 : 0; }
 
 namespace {
 __global__ void __launch_bounds__(256) check_codes_kernel(const int8_t* __restrict__ chars, size_t n, int32_t* bad) {
@@ -838,7 +891,7 @@ int rows_common_checks(sw_ctx* ctx, const int8_t* chars, const uint64_t* offsets
     if (gop > 0 || gex > 0) return fail(SW_ERR_INVALID, "gap scores must be <= 0");
     if (gop > gex) return fail(SW_ERR_INVALID, std::string(who) + " needs gop <= gex (the prefix form of the horizontal gap)");
     if (gex < -10000 || gop < -100000) return fail(SW_ERR_INVALID, std::string("gap score out of range for ") + who);
-    if (!ctx->have_matrix) return fail(SW_ERR_NO_MATRIX, "sw_set_matrix has not been called");
+    if (!have_scores(ctx)) return fail(SW_ERR_NO_MATRIX, "sw_set_matrix has not been called");
     if (!ctx->have_query) return fail(SW_ERR_NO_QUERY, "sw_set_query has not been called");
     if (n == 0) return SW_OK;
     if (!chars || !offsets || !lengths || !scores || !ids) return fail(SW_ERR_INVALID, "null buffer");
@@ -868,7 +921,7 @@ int pipeline_cpl(const sw_ctx* ctx, int32_t n, int32_t max_subject_len) {
     if (ctx->pipe_cpl == 4 || ctx->pipe_cpl == 8 || ctx->pipe_cpl == 16) return ctx->pipe_cpl;
     // (sw_rows_pipeline.hpp: batches of 8 rows for queries up to kPipeShortBatchMaxQuery, of 16 above)
     static const double kRowUs16[3] = {0.27, 0.38, 0.57}, kHopUs16[3] = {3.6, 5.0, 8.0}, kRowUs8[3] = {0.32, 0.42, 0.61}, kHopUs8[3] = {2.4, 3.4, 5.3};
-    const bool shortBatch = ctx->qlen <= swk::kPipeShortBatchMaxQuery;
+    const bool shortBatch = ctx->qlen <= swk::kPipeShortBatchMaxQuery || ctx->pssm_mode;   // (PSSM stages: always batches of 8)
     const double* kRowUs = shortBatch ? kRowUs8 : kRowUs16;
     const double* kHopUs = shortBatch ? kHopUs8 : kHopUs16;
     int best = 16;
@@ -900,7 +953,8 @@ namespace {
 int launch_pipeline(sw_ctx* ctx, swk::PipelineParams& p, int cpl, int64_t stages, int64_t tickets, uint32_t* start_signal, void* xfer,
                     hipStream_t stream) {
     const size_t need = kPipeCtrlBytes + (size_t)tickets * ((size_t)ctx->qlen + 1) * sizeof(unsigned long long);
-    p.query = ctx->d_query; p.qlen = ctx->qlen; p.matrix = ctx->d_matrix; p.dim = ctx->dim;
+    const bool pssm = ctx->pssm_mode;
+    p.query = pssm ? nullptr : ctx->d_query; p.qlen = ctx->qlen; p.matrix = pssm ? ctx->d_pssm : ctx->d_matrix; p.dim = pssm ? 0 : ctx->dim;
     // the launch's control words sit in front of its hand-off words, in the caller's buffer: one memset for both, and no
     // shared ring that a launch in flight on another stream could still be using
     p.ctrl = static_cast<uint32_t*>(xfer);
@@ -919,22 +973,23 @@ int launch_pipeline(sw_ctx* ctx, swk::PipelineParams& p, int cpl, int64_t stages
     SW_HIP(hipMemsetAsync(xfer, 0xFF, need, stream));   // "not written yet" / "minus one"
     const dim3 grid((unsigned)tickets), block(64);
     const int slot = ctx->pipe_slot;
-#define SW_PIPE_LAUNCH_B(CPL, B)                                                                                            \
-    do {                                                                                                                    \
-        if (slot == 128) hipLaunchKernelGGL((swk::sw_rows_pipeline_kernel<CPL, 128, B>), grid, block, 0, stream, p);        \
-        else if (slot == 168) hipLaunchKernelGGL((swk::sw_rows_pipeline_kernel<CPL, 168, B>), grid, block, 0, stream, p);   \
-        else if (slot == 256) hipLaunchKernelGGL((swk::sw_rows_pipeline_kernel<CPL, 256, B>), grid, block, 0, stream, p);   \
-        else hipLaunchKernelGGL((swk::sw_rows_pipeline_kernel<CPL, 0, B>), grid, block, 0, stream, p);                      \
+#define SW_PIPE_LAUNCH_BP(CPL, B, PSSM)                                                                                          \
+    do {                                                                                                                          \
+        if (slot == 128) hipLaunchKernelGGL((swk::sw_rows_pipeline_kernel<CPL, 128, B, PSSM>), grid, block, 0, stream, p);        \
+        else if (slot == 168) hipLaunchKernelGGL((swk::sw_rows_pipeline_kernel<CPL, 168, B, PSSM>), grid, block, 0, stream, p);   \
+        else if (slot == 256) hipLaunchKernelGGL((swk::sw_rows_pipeline_kernel<CPL, 256, B, PSSM>), grid, block, 0, stream, p);   \
+        else hipLaunchKernelGGL((swk::sw_rows_pipeline_kernel<CPL, 0, B, PSSM>), grid, block, 0, stream, p);                      \
     } while (0)
 #define SW_PIPE_LAUNCH(CPL)                                                                                              \
     do {                                                                                                                 \
-        if (ctx->qlen <= swk::kPipeShortBatchMaxQuery) SW_PIPE_LAUNCH_B(CPL, 8);                                         \
-        else SW_PIPE_LAUNCH_B(CPL, 16);                                                                                  \
+        if (pssm) SW_PIPE_LAUNCH_BP(CPL, 8, true);                                                                       \
+        else if (ctx->qlen <= swk::kPipeShortBatchMaxQuery) SW_PIPE_LAUNCH_BP(CPL, 8, false);                            \
+        else SW_PIPE_LAUNCH_BP(CPL, 16, false);                                                                          \
     } while (0)
     if (cpl == 4) SW_PIPE_LAUNCH(4);
     else if (cpl == 8) SW_PIPE_LAUNCH(8);
     else SW_PIPE_LAUNCH(16);
-#undef SW_PIPE_LAUNCH_B
+#undef SW_PIPE_LAUNCH_BP
 #undef SW_PIPE_LAUNCH
     SW_HIP(hipGetLastError());
     return SW_OK;
@@ -1199,13 +1254,13 @@ int sw_measure_valu_rate(sw_ctx* ctx, int mix, int millis, double* lane_instr_pe
 }
 
 int32_t sw_window_overlap(sw_ctx* ctx, int gop, int gex) {
-    if (!ctx || !ctx->have_query || !ctx->have_matrix) return -1;
+    if (!ctx || !ctx->have_query || !have_scores(ctx)) return -1;
     // every gap column costs at least min(|gop|, |gex|); an alignment with a positive score of a query of Q residues has at
     // most Q aligned columns worth at most max(M) each: fewer than Q * max(M) / cost gap columns, Q * (1 + max(M) / cost)
     // subject columns in all
     const int cost = std::min(-gop, -gex);
     if (cost <= 0) return -1;
-    const int64_t span = (int64_t)ctx->qlen + (int64_t)ctx->qlen * std::max(1, ctx->matrix_max) / cost + 1;
+    const int64_t span = (int64_t)ctx->qlen + (int64_t)ctx->qlen * score_max(ctx) / cost + 1;
     return span > 0x3fffffff ? -1 : (int32_t)span;
 }
 

@@ -42,6 +42,8 @@
 
 #include <type_traits>
 
+#include "sw_pssm.hpp"
+
 namespace swk {
 
 typedef uint32_t u32;
@@ -1400,6 +1402,10 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
 // ------------------------------------------------------------------------------------------------
 // Profile builder: tile[stripe][letter][chunk][lane][4 words] from the encoded query and the matrix.
 // Replaces the per-block pair-table construction of the reference (half2_kernels.cuh:57-65).
+//
+// Score source: the substitution table, indexed by the query's letters — or, when `query` is null, a position-specific
+// scoring matrix in its staged form (sw_pssm.hpp), indexed by the query POSITION; matrix21 then points to the staged PSSM
+// and pad_row to its first padding row (= qlen).  Everything behind the score (layout, frame terms, wide words) is shared.
 // ------------------------------------------------------------------------------------------------
 template <int KIND, int R, int LANES>
 __global__ void sw_build_profile_kernel(const int8_t* __restrict__ query, int32_t qlen,
@@ -1423,14 +1429,16 @@ __global__ void sw_build_profile_kernel(const int8_t* __restrict__ query, int32_
                 if (row_in_lane >= R) return 0u;  // unused upper half of an odd R's last word
                 const int64_t row = (int64_t)stripe * G::kStripeRows + lane * R + row_in_lane;
                 // matrix21: (query letters + one padding row `pad_row`) x 21 subject letters
-                const int qc = row < qlen ? (int)query[row] : pad_row;
+                const bool pssm = query == nullptr;
+                const int qc = row < qlen ? (pssm ? (int)row : (int)query[row]) : pad_row;
+                const int score = pssm ? (int)matrix21[pssm_index(qc, letter)] : (int)matrix21[qc * kLetters + letter];
                 // OFFS kernels (shift = a): the diagonal step raises the frame by a per column and by a per row class;
                 // the row above lane-local row 0 is the previous lane's last row (dp_step<OFFS>), whose frame lies a further
                 // a * head_extra below in the uniform frame (sw_scan_kernel; head_extra = 1; the column frame: 0)
                 const int P = frame_classes(A::kPacked, R, LANES, nstripes > 1, head_extra != 0);  // the scan kernel's (MULTI == more than one stripe)
                 const int cls = row_in_lane % P, above = (row_in_lane == 0 ? R - 1 : row_in_lane - 1) % P;
                 const int head = row_in_lane == 0 ? head_extra : 0;
-                return A::encode_score((int)matrix21[qc * kLetters + letter] + shift * (1 + head + cls - above));
+                return A::encode_score(score + shift * (1 + head + cls - above));
             };
             if constexpr (G::kWide) v = w < R ? (entry(w) | (A::kOne << 16)) : 0u;
             else if constexpr (A::kPacked) v = entry(2 * w) | (entry(2 * w + 1) << 16);

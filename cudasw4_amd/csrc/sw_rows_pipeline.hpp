@@ -38,6 +38,15 @@
 // VGPRs = what a wave of a four-, three- or two-waves-per-SIMD scan kernel takes): when it leaves, a queued wave of that
 // launch fits the hole exactly.
 //
+// Position-specific queries (PSSM = true; sw_pssm.hpp): there is no table to keep — every query row has its own 21 scores.
+// They come from the staged PSSM, whose tiles hold 16 rows transposed: lane j fetches the scores of subject letter j for a
+// whole batch of 8 rows with ONE aligned 8-byte load, prefetched like the hand-over words (kPipeDepth batches ahead, so
+// the load is long back when the batch starts), and picks one byte per row.  The row then is what a table register
+// was — lane j = the score against subject letter j — and the ds_bpermute behind it is unchanged.  The 26 table registers
+// are gone (2 registers per batch in flight instead); still no LDS, still exactly one register slot.  PSSM stages always
+// run batches of 8 rows: with batches of 16 the widest stage (16 columns per lane) came to 139 VGPRs, over the smallest
+// slot (128); with 8 it takes 99 (40 / 59 at 4 / 8 columns per lane), no scratch.
+//
 // int32 arithmetic; ~12 VALU instructions per cell (the scan kernels: 6.5) but 69 SIMDs instead of one for a
 // 35 000-residue subject: ~0.3 us per query row whatever the subject's length.
 #pragma once
@@ -45,6 +54,7 @@
 
 #include <cstdint>
 
+#include "sw_pssm.hpp"
 
 namespace swk {
 
@@ -61,7 +71,8 @@ struct PipelineParams {
     const int32_t* count_ptr;  // ... and its length on the device
     const int8_t* query;       // letter codes 0 .. dim-1; readable up to the next multiple of 16 behind qlen
     int32_t qlen;
-    const int8_t* matrix;      // (dim + 1) x 21 substitution scores, row = query letter
+    const int8_t* matrix;      // (dim + 1) x 21 substitution scores, row = query letter; PSSM kernels: the staged PSSM
+                               // (sw_pssm.hpp: pssm_staged_rows(qlen) rows), `query` and `dim` unused
     int32_t dim;
     int32_t gop, gex;          // <= 0, gop <= gex
     float* scores;
@@ -105,7 +116,22 @@ __device__ __forceinline__ unsigned long long pipe_pack(int lo, int hi) {
 
 constexpr int kPipeTableRows = 26;   // query letters (<= 25) + the padding row
 
-template <int CPL, int SLOT, int BATCH>
+// a batch of 8 PSSM rows as a lane holds it: byte r = the score of row r of the batch against the lane's subject letter
+struct PssmBatch {
+    uint32_t w0, w1;   // rows 0-3, 4-7
+    __device__ __forceinline__ static PssmBatch load(const int8_t* staged, int row0, int lane) {
+        // row0 is a multiple of 8: the batch is one half of a tile row of 16 bytes
+        const uint2 v = *reinterpret_cast<const uint2*>(staged + pssm_index(row0, lane & (kPssmTileLetters - 1)));
+        return PssmBatch{v.x, v.y};
+    }
+    // the score of row r of a batch whose words are b0, b1, sign-extended.  r is wave-uniform: the word is chosen by a scalar
+    // condition, the byte by v_bfe_i32 with a scalar offset
+    __device__ __forceinline__ static int row(uint32_t b0, uint32_t b1, int r) {
+        return __builtin_amdgcn_sbfe((int)((r & 4) ? b1 : b0), (uint32_t)(r & 3) * 8u, 8u);
+    }
+};
+
+template <int CPL, int SLOT, int BATCH, bool PSSM = false>
 __global__ void __launch_bounds__(64) sw_rows_pipeline_kernel(const PipelineParams p) {
     constexpr int kPipeBatch = BATCH, kPipeDepth = BATCH <= 8 ? 2 : 1;
     // the wave's register allocation is what the highest register it names says: claim the whole slot
@@ -143,9 +169,12 @@ __global__ void __launch_bounds__(64) sw_rows_pipeline_kernel(const PipelinePara
 
     // substitution scores: register q holds query letter q's row, lane j the score against subject letter j; "letter" 21 =
     // a position behind the subject's end scores -30000 against everything, so nothing positive ever starts there
-    int tbl[kPipeTableRows];
+    // (PSSM: no table — the rows come from memory, batch by batch)
+    int tbl[PSSM ? 1 : kPipeTableRows];
+    if constexpr (!PSSM) {
 #pragma unroll
-    for (int q = 0; q < kPipeTableRows; q++) tbl[q] = (q <= p.dim && lane < 21) ? (int)p.matrix[q * 21 + lane] : -30000;
+        for (int q = 0; q < kPipeTableRows; q++) tbl[q] = (q <= p.dim && lane < 21) ? (int)p.matrix[q * 21 + lane] : -30000;
+    }
 
     const int8_t* const s = p.chars + (p.offsets[pos] - p.offsets[0]);
     const int col0 = (stage * 64 + lane) * CPL;   // first owned column (0-based)
@@ -203,6 +232,14 @@ __global__ void __launch_bounds__(64) sw_rows_pipeline_kernel(const PipelinePara
     unsigned long long pend[kPipeDepth];
 #pragma unroll
     for (int d = 0; d < kPipeDepth; d++) pend[d] = stage > 0 ? pipe_load(xin + min(d * kPipeBatch + sl, p.qlen)) : kNoLeft;
+    // PSSM rows: the batches in flight, oldest first; requests beyond the query's last batch repeat that one (never used)
+    const int lastBatch = (p.qlen - 1) / kPipeBatch * kPipeBatch;
+    static_assert(!PSSM || BATCH == 8, "PSSM stages run batches of 8 rows");
+    PssmBatch prow[kPipeDepth];
+    if constexpr (PSSM) {
+#pragma unroll
+        for (int d = 0; d < kPipeDepth; d++) prow[d] = PssmBatch::load(p.matrix, min(d * kPipeBatch, lastBatch), lane);
+    }
     for (int i0 = 0; i0 < p.qlen; i0 += kPipeBatch) {
         const int nrows = __builtin_amdgcn_readfirstlane(min(kPipeBatch, p.qlen - i0));
         unsigned long long cur = pend[0];
@@ -215,9 +252,29 @@ __global__ void __launch_bounds__(64) sw_rows_pipeline_kernel(const PipelinePara
         }
         const int curLo = (int)(uint32_t)cur, curHi = (int)(uint32_t)(cur >> 32);
         // lane r holds query letter i0 + r (letters behind the query's end are never used)
-        const int qvec = (int)p.query[i0 + sl];
+        int qvec = 0;
+        uint32_t b0 = 0, b1 = 0;
+        if constexpr (PSSM) {
+            const PssmBatch rows = prow[0];
+#pragma unroll
+            for (int d = 0; d + 1 < kPipeDepth; d++) prow[d] = prow[d + 1];
+            prow[kPipeDepth - 1] = PssmBatch::load(p.matrix, min(i0 + kPipeDepth * kPipeBatch, lastBatch), lane);
+            // The batch's two words, pinned to registers of their own for the row loop.  Left as members of the struct, the
+            // optimiser folds "select one of the loaded words" into "load through a selected address": an indexed array, which
+            // for a kernel means LDS (or scratch) — and a stage must use neither.
+            b0 = rows.w0; b1 = rows.w1;
+            asm volatile("" : "+v"(b0), "+v"(b1));
+        } else {
+            qvec = (int)p.query[i0 + sl];
+        }
         for (int r = 0; r < nrows; r++) {
-            const int rowv = tbl[__builtin_amdgcn_readlane(qvec, r)];   // (a uniform index into registers: v_movrels)
+            int rowv;
+            if constexpr (PSSM) {
+                const int v = PssmBatch::row(b0, b1, r);
+                rowv = lane < 21 ? v : -30000;   // "letter" 21 = behind the subject's end, as in the table
+            } else {
+                rowv = tbl[__builtin_amdgcn_readlane(qvec, r)];   // (a uniform index into registers: v_movrels)
+            }
             const int carryIn = __builtin_amdgcn_readlane(curLo, r);
             const int hlIn = __builtin_amdgcn_readlane(curHi, r);   // H(i, col0 - 1) of lane 0: next row's diagonal input
 

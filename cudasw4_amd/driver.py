@@ -23,7 +23,7 @@ EXPORTS = ["swdrv_last_error", "swdrv_create", "swdrv_destroy", "swdrv_open_db",
            "swdrv_cached_chars", "swdrv_streamed_bytes", "swdrv_plan_residency", "swdrv_numa_node", "swdrv_device_of",
            "swdrv_bind_to_numa_node", "swdrv_device_numa_node", "swdrv_window_stats", "swdrv_service_launches",
            "swdrv_tail_overlaps", "swdrv_prefers_two_in_flight", "swdrv_pipeline_launches", "swdrv_handshake_active", "swdrv_preferred_in_flight",
-           "swdrv_latency_scans", "swdrv_plan_runs_mode", "swdrv_align_hits"]
+           "swdrv_latency_scans", "swdrv_plan_runs_mode", "swdrv_align_hits", "swdrv_scan_pssm", "swdrv_scan_submit_pssm"]
 
 
 class DriverError(RuntimeError):
@@ -124,6 +124,17 @@ def _align_fn():
         vp = ctypes.c_void_p
         f.argtypes = [vp, ctypes.c_char_p, ctypes.c_int32, vp, vp, ctypes.c_int, vp, vp, ctypes.c_int64]
     return f
+
+
+def _pssm_fns():
+    """swdrv_scan_pssm / swdrv_scan_submit_pssm, bound on first use (like swdrv_align_hits: not in every build of this C ABI)"""
+    scan, submit = lib.swdrv_scan_pssm, lib.swdrv_scan_submit_pssm
+    if scan.argtypes is None:
+        vp = ctypes.c_void_p
+        scan.argtypes = [vp, vp, ctypes.c_int32, vp, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                         ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
+        submit.argtypes = [vp, vp, ctypes.c_int32]
+    return scan, submit
 
 
 # ---- input helpers of the host library (what `align` does to its inputs; no GPU needed) ----
@@ -418,6 +429,29 @@ class Driver:
         return {"scores": scores[:n].copy(), "ids": ids[:n].copy(), "num_overflows": novf.value,
                 "num_rescored": int(lib.swdrv_last_rescored(self.handle)),
                 "seconds": sec.value, "gcups": gcups.value}
+
+    def scan_pssm(self, pssm):
+        """scan() with a position-specific scoring matrix as the query: (qlen, 21) int8, row i = query position i, column c =
+        subject code c, column 20 negative (cudasw4_amd.pssm).  Same result dict as scan()."""
+        from . import pssm as _pssm
+        m = _pssm.as_pssm(pssm)
+        cap = max(self.num_top, 1)
+        scores = np.zeros(cap, dtype=np.int32)
+        ids = np.zeros(cap, dtype=np.int64)
+        nres, novf = ctypes.c_int(), ctypes.c_int()
+        sec, gcups = ctypes.c_double(), ctypes.c_double()
+        _check(_pssm_fns()[0](self.handle, m.ctypes.data, m.shape[0], scores.ctypes.data, ids.ctypes.data, cap,
+                              ctypes.byref(nres), ctypes.byref(novf), ctypes.byref(sec), ctypes.byref(gcups)))
+        n = nres.value
+        return {"scores": scores[:n].copy(), "ids": ids[:n].copy(), "num_overflows": novf.value,
+                "num_rescored": int(lib.swdrv_last_rescored(self.handle)),
+                "seconds": sec.value, "gcups": gcups.value}
+
+    def submit_pssm(self, pssm):
+        """submit() with a PSSM query; collect() returns its results.  May be in flight together with a letter query."""
+        from . import pssm as _pssm
+        m = _pssm.as_pssm(pssm)
+        _check(_pssm_fns()[1](self.handle, m.ctypes.data, m.shape[0]))
 
     def submit(self, query_letters):
         """First half of scan(): enqueue the query on every GPU without waiting (at most two in flight)."""

@@ -69,6 +69,15 @@ int swdrv_scan_collect(swdrv* d, int32_t* scores, int64_t* ids, int cap, int* nr
                        double* gcups);
 int swdrv_in_flight(swdrv* d);
 
+/* Profile search (an extension; include/cudasw4_amd_pssm.h): the query is a position-specific scoring matrix, qlen x 21
+ * int8, row i = query position i, column c = dbdata subject code c (0..19 = ARNDCQEGHILKMFPSTWYV, 20 = other / padding:
+ * negative in every row).  The driver's matrix is not used; its gap scores, shards, residency, streaming and merge are, and
+ * the results have the layout of swdrv_scan's.  swdrv_scan_submit_pssm pairs with swdrv_scan_collect, so a PSSM query and
+ * a letter query can be in flight together.  swdrv_align_hits does not apply to the hits of a PSSM query. */
+int swdrv_scan_pssm(swdrv* d, const int8_t* pssm, int32_t qlen, int32_t* scores, int64_t* ids, int cap,
+                    int* nres, int* num_overflows, double* seconds, double* gcups);
+int swdrv_scan_submit_pssm(swdrv* d, const int8_t* pssm, int32_t qlen);
+
 /* ---- measurement / verification hooks (bench.py, tests) ----
  * Kernel events: HIP events around every DP launch on the stream it runs on.  take: 15 doubles per launch
  * (gpu index, kind, part_id, query length, subjects, cells, padded subject bytes, milliseconds, begin ms, end ms — these

@@ -1,0 +1,45 @@
+/* cudasw4_amd_pssm.h — profile search: a position-specific scoring matrix (PSSM) as the query of libcudasw4_amd.so.
+ *
+ * An extension (the reference scores residue strings only).  A PSSM query of qlen positions is qlen x 21 int8 scores:
+ * row i = query position i, column c = dbdata subject code c (0..19 = ARNDCQEGHILKMFPSTWYV, 20 = "other" and the
+ * padding of the dbdata layout).  It takes the place of the pair (sw_set_matrix, sw_set_query): where a letter query
+ * scores position i against subject letter c with matrix[query[i]][c], a PSSM query scores it with pssm[i][c].
+ * Everything else — recurrence, gap model, overflow and re-score rules, top-K, result layout — is that of a letter
+ * query, and every scan path of cudasw4_amd.h / cudasw4_amd_engine.h serves both.  A PSSM whose row i is the table row
+ * of letter i of a string reproduces that string's scores bit for bit.
+ */
+#ifndef CUDASW4_AMD_PSSM_H
+#define CUDASW4_AMD_PSSM_H
+
+#include "cudasw4_amd.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define SW_PSSM_COLUMNS 21
+/* longest PSSM query (the device form takes 32 bytes per position) */
+#define SW_PSSM_MAX_QUERY_LEN (1 << 22)
+
+/* Install a PSSM as the context's query (HOST pointer, row-major qlen x SW_PSSM_COLUMNS int8).
+ *   CONTRACT: column 20 of every row must be negative (padding has to neutralise itself: the condition sw_set_matrix
+ *   imposes on a table); otherwise any int8 value is allowed.  The rows that pad the query to the kernels' tile are
+ *   the library's business.
+ * Staging is that of sw_set_query: the scores are copied into a pinned buffer of the context (the caller's buffer is
+ * free again on return), the upload is enqueued on `stream` behind the scans of the previous query, and the call does
+ * not wait for the GPU.  Needs no sw_set_matrix.  From here on EVERY scan entry point scores with the PSSM —
+ * sw_scan_partition, sw_rescore_overflow[_stat], sw_scan_batch with everything it launches (bulk and side launches, row
+ * pipelines, windows, the re-score service), and the planning calls (sw_plan_launch, sw_scan_temp_bytes,
+ * sw_query_length) describe it — until the next sw_set_query (back to letters) or sw_set_query_pssm.  Bounds that a
+ * letter query derives from the largest entry of the substitution table (the int32 kind served in fp32 lanes, the
+ * overlap of windows) are derived from the largest entry of the PSSM.
+ * sw_align_hits is not affected: it takes its query as an argument and scores with the context's matrix. */
+int sw_set_query_pssm(sw_ctx* ctx, const int8_t* pssm_host, int32_t qlen, void* stream);
+
+/* 1 when the context's current query is a PSSM, 0 for a letter query or none. */
+int sw_query_is_pssm(const sw_ctx* ctx);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* CUDASW4_AMD_PSSM_H */
