@@ -34,7 +34,7 @@ EXPORTS = ["sw_batch_create", "sw_batch_destroy", "sw_scan_batch", "sw_batch_joi
            "sw_set_rows_pipeline_slot", "sw_rescore_overflow_pipelined", "sw_rescore_overflow_pipelined_temp_bytes", "sw_measure_valu_rate",
            "sw_align_hits"]
 # ... and include/cudasw4_amd_pssm.h (profile search: a position-specific scoring matrix as the query)
-PSSM_EXPORTS = ["sw_set_query_pssm", "sw_query_is_pssm"]
+PSSM_EXPORTS = ["sw_set_query_pssm", "sw_query_is_pssm", "sw_align_hits_pssm"]
 
 
 # sw_align_hits (include/cudasw4_amd.h): result records, statuses, flags, CIGAR op codes
@@ -284,6 +284,25 @@ def align_hits(ctx, query, qlen, n, chars, offsets, lengths, max_subject_len, go
                    cigar_offsets, flags, trace_bytes, temp, temp_bytes, ctypes.pointer(need),
                    ctypes.cast(ev, ctypes.c_void_p) if ev is not None else None, stream)
     check(lib.sw_align_hits(ctx.handle if ctx is not None else None, ctypes.byref(a)))
+    return int(need.value)
+
+
+def align_hits_pssm(ctx, pssm, consensus, qlen, n, chars, offsets, lengths, max_subject_len, gop, gex, results, cigar=0,
+                    cigar_offsets=0, expected_scores=0, flags=0, trace_bytes=0, temp=0, temp_bytes=0, stream=0, phase_events=None):
+    """sw_align_hits_pssm: align_hits with a PSSM as the query.  pssm: device pointer to qlen x 21 int8 (row-major);
+    consensus: device pointer to qlen codes, or 0 (the best-scoring standard residue of every row).  The other arguments
+    and the return value are those of align_hits."""
+    if not hasattr(lib, "sw_align_hits_pssm"):
+        raise SwError(-1, "this build of libcudasw4_amd.so has no sw_align_hits_pssm")
+    f = lib.sw_align_hits_pssm
+    if f.argtypes is None:   # bound on first use (CUDASW4_AMD_LIB may name an older build)
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(_AlignArgs), ctypes.c_void_p]
+    need = ctypes.c_size_t(0)
+    ev = (ctypes.c_void_p * 4)(*phase_events) if phase_events is not None else None
+    a = _AlignArgs(consensus or None, qlen, n, chars, offsets, lengths, max_subject_len, gop, gex, expected_scores, results, cigar,
+                   cigar_offsets, flags, trace_bytes, temp, temp_bytes, ctypes.pointer(need),
+                   ctypes.cast(ev, ctypes.c_void_p) if ev is not None else None, stream)
+    check(f(ctx.handle if ctx is not None else None, ctypes.byref(a), pssm or None))
     return int(need.value)
 
 

@@ -38,7 +38,7 @@ struct AlignmentColumns {
     }
 };
 
-// alignments: nullptr without --alignments, else one per result
+// alignments: nullptr without --alignments / --pssmAlignments, else one per result
 void printScanResultPlain(std::ostream& os, const ScanResult& r, const SearchDriver& d, const std::vector<HitAlignment>* alignments = nullptr) {
     for (size_t i = 0; i < r.scores.size(); i++) {
         const int64_t id = r.referenceIds[i];
@@ -96,7 +96,7 @@ void reportScan(const ProgramOptions& o, const ScanResult& r) {
 // collect).  On large DBs two queries in flight bring nothing (10^6 subjects) or cost (-0.8 % on a Swiss-Prot-like one);
 // CUDASW4_AMD_PIPELINE=0 keeps one query at a time everywhere.  Output order and format are the reference's either way; a
 // query's line is printed when its results are in.
-// aligner: non-null with --alignments (every query's hits are aligned right after its collect, against that query)
+// aligner: non-null with --alignments / --pssmAlignments (every query's hits are aligned right after its collect, against that query)
 void processQueryFile(const std::string& file, const ProgramOptions& o, SearchDriver& driver, std::ostream& out, bool interactive,
                       HitAligner* aligner) {
     SequenceReader reader(file);
@@ -152,7 +152,8 @@ void processQueryFile(const std::string& file, const ProgramOptions& o, SearchDr
 }
 
 // One --pssm file: a single query (number 0 of its "file"), printed like a query of a query file; header = the file's base name
-void processPssmQuery(const PssmQuery& q, const ProgramOptions& o, SearchDriver& driver, std::ostream& out) {
+// aligner: non-null with --pssmAlignments (the hits are aligned against the PSSM; '=' / 'X' against the file's residue column)
+void processPssmQuery(const PssmQuery& q, const ProgramOptions& o, SearchDriver& driver, std::ostream& out, HitAligner* aligner) {
     driver.totalTimerStart();
     std::cout << "Processing query " << 0 << " ... ";
     std::cout.flush();
@@ -160,11 +161,14 @@ void processPssmQuery(const PssmQuery& q, const ProgramOptions& o, SearchDriver&
     ScanResult r = driver.collect();
     reportScan(o, r);
     if (o.numTopOutputs > 0) {
+        std::vector<HitAlignment> alignments;
+        if (aligner) alignments = aligner->align(q.scores.data(), q.length(), q.consensus.data(), r);
+        const std::vector<HitAlignment>* al = aligner ? &alignments : nullptr;
         if (o.outputMode == ProgramOptions::OutputMode::Plain) {
             out << "Query " << 0 << ", header " << q.name << ", length " << q.length() << ", num overflows " << r.stats.numOverflows << "\n";
-            printScanResultPlain(out, r, driver);
+            printScanResultPlain(out, r, driver, al);
         } else {
-            printScanResultTSV(out, r, driver, 0, int64_t(q.length()), q.name);
+            printScanResultTSV(out, r, driver, 0, int64_t(q.length()), q.name, al);
         }
         out.flush();
     }
@@ -184,8 +188,8 @@ int main(int argc, char** argv) {
     printOptions(options);
     try {
         // PSSM queries are read and validated before any device is opened: a malformed file is an error of the command line
-        if (!options.pssmFiles.empty() && options.alignments)
-            throw std::runtime_error("--pssm cannot be combined with --alignments: hit alignment of PSSM queries is not supported");
+        if (!options.pssmFiles.empty() && options.alignments && !options.pssmAlignments)
+            throw std::runtime_error("--pssm cannot be combined with --alignments: use --pssmAlignments to align the results of every query, PSSM queries included");
         if (!options.pssmFiles.empty() && options.interactive)
             throw std::runtime_error("--pssm cannot be combined with --interactive");
         std::vector<PssmQuery> pssmQueries;
@@ -210,7 +214,7 @@ int main(int argc, char** argv) {
         }
         std::ofstream outputfile(options.outputfile);
         if (!outputfile) throw std::runtime_error("Cannot open file " + options.outputfile);
-        if (options.outputMode == ProgramOptions::OutputMode::TSV) printTSVHeader(outputfile, options.alignments);
+        if (options.outputMode == ProgramOptions::OutputMode::TSV) printTSVHeader(outputfile, options.reportAlignments());
 
         SearchDriver driver(deviceIds, options.numTopOutputs, options.matrix, options.kernels, options.memory, options.verbose,
                             options.effectiveGop(), options.effectiveGex());
@@ -235,13 +239,13 @@ int main(int argc, char** argv) {
         }
         if (options.loadFullDBToGpu) driver.prefetchDBToGpus();
         std::unique_ptr<HitAligner> aligner;
-        if (options.alignments) aligner = std::make_unique<HitAligner>(driver);
+        if (options.reportAlignments()) aligner = std::make_unique<HitAligner>(driver);
 
         if (!options.interactive) {
             size_t nextPssm = 0;
             for (const auto& input : options.inputs) {
                 std::cout << "Processing query file " << input.path << "\n";
-                if (input.pssm) processPssmQuery(pssmQueries[nextPssm++], options, driver, outputfile);
+                if (input.pssm) processPssmQuery(pssmQueries[nextPssm++], options, driver, outputfile, aligner.get());
                 else processQueryFile(input.path, options, driver, outputfile, false, aligner.get());
             }
         } else {

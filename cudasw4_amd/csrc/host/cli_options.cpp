@@ -33,6 +33,7 @@ void printOptions(const ProgramOptions& o) {
     std::cout << "maxTempBytes: " << o.memory.maxTempBytes << "\n";
     for (size_t i = 0; i < o.queryFiles.size(); i++) std::cout << "queryFile " << i << " : " << o.queryFiles[i] << "\n";
     for (size_t i = 0; i < o.pssmFiles.size(); i++) std::cout << "pssmFile " << i << " : " << o.pssmFiles[i] << "\n";
+    if (o.pssmAlignments) std::cout << "pssmAlignments: " << o.pssmAlignments << "\n";
     std::cout << "blosum: " << substitution_matrix(o.matrix).name << "\n";
     std::cout << "singlePassType: " << to_string(o.kernels.singlePassType) << "\n";
     std::cout << "manyPassType_small: " << to_string(o.kernels.manyPassType_small) << "\n";
@@ -70,6 +71,7 @@ bool parseArgs(int argc, char** argv, ProgramOptions& o) {
         else if (arg == "--verbose") o.verbose = true;
         else if (arg == "--interactive") o.interactive = true;
         else if (arg == "--alignments") o.alignments = true;
+        else if (arg == "--pssmAlignments") o.pssmAlignments = true;
         else if (arg == "--printLengthPartitions") o.printLengthPartitions = true;
         else if (arg == "--prefetchDBFile") o.prefetchDBFile = true;
         else if (arg == "--top") o.numTopOutputs = std::atoi(value(i).c_str());
@@ -127,7 +129,7 @@ void printHelp(char** argv) {
     std::cout << "   Mandatory\n";
     std::cout << "      --query queryfile : Mandatory. Fasta or Fastq. Can be gzip'ed. Repeat this option for multiple query files\n";
     std::cout << "      --pssm pssmfile : A position-specific scoring matrix as a query, in place of or beside --query: an NCBI ASCII PSSM\n"
-                 "        (psiblast -out_ascii_pssm). Repeat this option for multiple PSSMs. Not with --alignments\n";
+                 "        (psiblast -out_ascii_pssm). Repeat this option for multiple PSSMs. Alignments of its results: --pssmAlignments (not --alignments)\n";
     std::cout << "      --db dbPrefix : Mandatory. The DB to query against. The same dbPrefix as used for makedb\n\n";
     std::cout << "   Scoring\n";
     std::cout << "      --top val : Output the val best scores. Default val = " << d.numTopOutputs << "\n";
@@ -146,6 +148,7 @@ void printHelp(char** argv) {
     std::cout << "      --of : Result output file. Parent directory must exist. Default: console output (/dev/stdout)\n";
     std::cout << "      --tsv : Print results as tab-separated values instead of plain text. \n";
     std::cout << "      --alignments : Also report where every result aligns: query and reference begin / end, alignment length, identities, gap opens and CIGAR (computed on the GPU).\n";
+    std::cout << "      --pssmAlignments : --alignments for every query, --pssm queries included. Identities and the CIGAR's = / X of a PSSM are counted against the residue column of its file.\n";
     std::cout << "      --verbose : More console output. Shows timings. \n";
     std::cout << "      --printLengthPartitions : Print number of sequences per length partition in db.\n";
     std::cout << "      --interactive : Loads DB, then waits for sequence input by user\n";

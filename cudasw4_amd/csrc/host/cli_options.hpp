@@ -21,6 +21,10 @@ struct ProgramOptions {
     bool interactive = false;
     bool verbose = false;
     bool alignments = false;     // --alignments: coordinates and CIGAR of every result (hit_alignment.hpp); an extension
+    // --pssmAlignments: --alignments for every query of the command line, --pssm queries included (identities and '=' / 'X'
+    // of a PSSM against the residue column of its file)
+    bool pssmAlignments = false;
+    bool reportAlignments() const { return alignments || pssmAlignments; }
     bool prefetchDBFile = false;
     int numTopOutputs = 10;
     int gop = -11;

@@ -1,7 +1,8 @@
-// hit_alignment.cpp — HitAligner and swdrv_align_hits: the top hits of a scan aligned with sw_align_hits.
+// hit_alignment.cpp — HitAligner, swdrv_align_hits and swdrv_align_hits_pssm: the top hits of a scan aligned with
+// sw_align_hits (letter queries) or sw_align_hits_pssm (PSSM queries).
 //
 // Kept out of search_driver.cpp and driver_capi.cpp on purpose: tests/host/fake_gpu links exactly those files against a
-// fake of the C ABI that has no sw_align_hits.
+// fake of the C ABI that has neither.
 #include "hit_alignment.hpp"
 
 #include <algorithm>
@@ -10,6 +11,7 @@
 #include <string>
 
 #include "../../../include/cudasw4_amd_driver.h"
+#include "../../../include/cudasw4_amd_pssm.h"
 #include "driver_handle.hpp"
 #include "sequence_codec.hpp"
 
@@ -88,13 +90,37 @@ std::vector<HitAlignment> HitAligner::align(const char* query, int32_t qlen, con
 
 std::vector<HitAlignment> HitAligner::align(const char* query, int32_t qlen, const int64_t* ids, const int32_t* scores,
                                             size_t n) {
-    std::vector<HitAlignment> out(n);
-    if (n == 0) return out;
+    if (n == 0) return std::vector<HitAlignment>();
     if (qlen <= 0 || !query || !ids || !scores) throw std::runtime_error("hit alignment: empty query or null hit list");
     // the query encoded as the scan encoded it
     const SubstitutionMatrix& m = d_.matrix();
     std::vector<int8_t> q(static_cast<size_t>(qlen));
     for (int32_t i = 0; i < qlen; i++) q[size_t(i)] = m.dim == 25 ? encode_residue25(query[i]) : encode_residue(query[i]);
+    return run(q.data(), nullptr, qlen, ids, scores, n);
+}
+
+std::vector<HitAlignment> HitAligner::align(const int8_t* pssm, int32_t qlen, const char* consensus, const ScanResult& r) {
+    return align(pssm, qlen, consensus, r.referenceIds.data(), r.scores.data(), r.scores.size());
+}
+
+std::vector<HitAlignment> HitAligner::align(const int8_t* pssm, int32_t qlen, const char* consensus, const int64_t* ids,
+                                            const int32_t* scores, size_t n) {
+    if (n == 0) return std::vector<HitAlignment>();
+    if (qlen <= 0 || !pssm || !ids || !scores) throw std::runtime_error("hit alignment: empty PSSM or null hit list");
+    for (int32_t i = 0; i < qlen; i++)
+        if (pssm[size_t(i) * SW_PSSM_COLUMNS + 20] >= 0)
+            throw std::runtime_error("hit alignment: PSSM row " + std::to_string(i) + ": column 20 (other / padding) must be negative");
+    std::vector<int8_t> c;
+    if (consensus) {
+        c.resize(static_cast<size_t>(qlen));
+        for (int32_t i = 0; i < qlen; i++) c[size_t(i)] = encode_residue(consensus[i]);
+    }
+    return run(consensus ? c.data() : nullptr, pssm, qlen, ids, scores, n);
+}
+
+std::vector<HitAlignment> HitAligner::run(const int8_t* codes, const int8_t* pssm, int32_t qlen, const int64_t* ids,
+                                          const int32_t* scores, size_t n) {
+    std::vector<HitAlignment> out(n);
     // the hit subjects in dbdata layout, from the host copy of the DB (resident, streamed, pseudo and array DBs alike)
     std::vector<int8_t> chars;
     std::vector<uint64_t> offsets(n + 1, 0);
@@ -128,7 +154,8 @@ std::vector<HitAlignment> HitAligner::align(const char* query, int32_t qlen, con
         return dst;
     };
     sw_align_args a{};
-    a.query = static_cast<const int8_t*>(put(kQuery, q.data(), q.size()));
+    a.query = codes ? static_cast<const int8_t*>(put(kQuery, codes, size_t(qlen))) : nullptr;
+    const int8_t* devPssm = pssm ? static_cast<const int8_t*>(put(kPssm, pssm, size_t(qlen) * SW_PSSM_COLUMNS)) : nullptr;
     a.qlen = qlen;
     a.n = int32_t(n);
     a.chars = static_cast<const int8_t*>(put(kChars, chars.data(), chars.size()));
@@ -145,7 +172,8 @@ std::vector<HitAlignment> HitAligner::align(const char* query, int32_t qlen, con
     a.temp = grow(kTemp, tempBytes);
     a.temp_bytes = tempBytes;
     a.stream = stream_;
-    sw_check(sw_align_hits(ctx_, &a), "sw_align_hits");
+    if (pssm) sw_check(sw_align_hits_pssm(ctx_, &a, devPssm), "sw_align_hits_pssm");
+    else sw_check(sw_align_hits(ctx_, &a), "sw_align_hits");
     std::vector<sw_align_result> res(n);
     std::vector<uint32_t> cigar(static_cast<size_t>(cigarOffsets[n]));
     hip_check(hipMemcpyAsync(res.data(), a.results, n * sizeof(sw_align_result), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync");
@@ -167,13 +195,17 @@ std::vector<HitAlignment> HitAligner::align(const char* query, int32_t qlen, con
 }  // namespace swh
 
 #ifdef SWH_DRIVER_CAPI   // libcudasw4_host.so (with driver_capi.cpp); `align` links the class alone
-extern "C" int swdrv_align_hits(swdrv* d, const char* query, int32_t qlen, const int64_t* ids, const int32_t* scores, int n,
-                                sw_align_result* results, uint32_t* cigar, int64_t cigar_cap) {
+namespace {
+
+// query != nullptr: the letter form; else the PSSM form
+int align_hits_capi(swdrv* d, const char* query, const int8_t* pssm, const char* consensus, int32_t qlen, const int64_t* ids,
+                    const int32_t* scores, int n, sw_align_result* results, uint32_t* cigar, int64_t cigar_cap) {
     try {
         if (!d || !d->driver) throw std::runtime_error("null driver");
         if (n < 0 || (n > 0 && (!results || (!cigar && cigar_cap > 0)))) throw std::runtime_error("bad output arguments");
         swh::HitAligner aligner(*d->driver);
-        const std::vector<swh::HitAlignment> hits = aligner.align(query, qlen, ids, scores, size_t(n));
+        const std::vector<swh::HitAlignment> hits = pssm ? aligner.align(pssm, qlen, consensus, ids, scores, size_t(n))
+                                                         : aligner.align(query, qlen, ids, scores, size_t(n));
         int64_t used = 0;
         for (size_t i = 0; i < hits.size(); i++) {
             results[i] = hits[i].r;
@@ -187,5 +219,21 @@ extern "C" int swdrv_align_hits(swdrv* d, const char* query, int32_t qlen, const
         swh::set_driver_error(e.what());
         return -1;
     }
+}
+
+}  // namespace
+
+extern "C" int swdrv_align_hits(swdrv* d, const char* query, int32_t qlen, const int64_t* ids, const int32_t* scores, int n,
+                                sw_align_result* results, uint32_t* cigar, int64_t cigar_cap) {
+    return align_hits_capi(d, query, nullptr, nullptr, qlen, ids, scores, n, results, cigar, cigar_cap);
+}
+
+extern "C" int swdrv_align_hits_pssm(swdrv* d, const int8_t* pssm, int32_t qlen, const char* consensus, const int64_t* ids,
+                                     const int32_t* scores, int n, sw_align_result* results, uint32_t* cigar, int64_t cigar_cap) {
+    if (!pssm) {
+        swh::set_driver_error("hit alignment: null PSSM");
+        return -1;
+    }
+    return align_hits_capi(d, nullptr, pssm, consensus, qlen, ids, scores, n, results, cigar, cigar_cap);
 }
 #endif

@@ -1,5 +1,6 @@
-// hit_alignment.hpp — coordinates and CIGAR of a scan's top hits (sw_align_hits, include/cudasw4_amd.h), run after
-// SearchDriver::collect().  An extension: the reference reports scores only.
+// hit_alignment.hpp — coordinates and CIGAR of a scan's top hits (sw_align_hits, include/cudasw4_amd.h; for the hits of a
+// PSSM query sw_align_hits_pssm, include/cudasw4_amd_pssm.h), run after SearchDriver::collect().  An extension: the
+// reference reports scores only.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -34,13 +35,25 @@ public:
     std::vector<HitAlignment> align(const char* query, int32_t qlen, const int64_t* ids, const int32_t* scores, size_t n);
     std::vector<HitAlignment> align(const char* query, int32_t qlen, const ScanResult& r);
 
+    // The hits of a PSSM query (pssm: qlen x 21 int8 row-major, host; column 20 negative in every row).  consensus: qlen
+    // residue letters that '=' / 'X' and the identities are counted against (encode_residue: a non-standard letter, '*'
+    // or '-' is identical to nothing), or nullptr: the best-scoring standard residue of every row.  The driver's gap
+    // scores apply, its matrix does not.
+    std::vector<HitAlignment> align(const int8_t* pssm, int32_t qlen, const char* consensus, const int64_t* ids,
+                                    const int32_t* scores, size_t n);
+    std::vector<HitAlignment> align(const int8_t* pssm, int32_t qlen, const char* consensus, const ScanResult& r);
+
 private:
+    // both forms behind the encoding of the query.  pssm == nullptr: `codes` are the query's codes; else `codes` are the
+    // consensus codes (nullptr: none)
+    std::vector<HitAlignment> run(const int8_t* codes, const int8_t* pssm, int32_t qlen, const int64_t* ids,
+                                  const int32_t* scores, size_t n);
     void* grow(size_t slot, size_t bytes);
     const SearchDriver& d_;
     int device_ = 0;
     sw_ctx* ctx_ = nullptr;
     hipStream_t stream_ = nullptr;
-    enum { kQuery, kChars, kOffsets, kLengths, kScores, kResults, kCigar, kCigarOffsets, kTemp, kBuffers };
+    enum { kQuery, kPssm, kChars, kOffsets, kLengths, kScores, kResults, kCigar, kCigarOffsets, kTemp, kBuffers };
     void* buf_[kBuffers] = {};
     size_t cap_[kBuffers] = {};
 };

@@ -20,6 +20,12 @@
 // Direction bits of (c): kRows x 4 bits = one dword per lane and step, stored at [stripe][step][lane], so the 64
 // stores of one step are contiguous.  Per cell: bits 0-1 where H came from (0 diagonal, 1 E, 2 F; ties in that order),
 // bit 2 E extended (else opened), bit 3 F extended.  Only vector stores are used.
+//
+// PSSM form (sw_align_hits_pssm, DESIGN.md "Hit alignment of PSSM queries"): the substitution score of row i is
+// pssm[i][s_j] in place of M[q_i][s_j].  dp_pass<MODE, true> keeps the step loop and takes the scores from an LDS tile of
+// the stripe's 512 PSSM rows, laid out [row-in-lane r][letter][lane] in dwords: lane l reads word (r * 21 + letter) * 64
+// + l, which lies in bank l whatever letters the 64 lanes look up.  The tile is reloaded at the start of every stripe
+// (load_tile); the letter form is the template's other instantiation and compiles to what it was before the template.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -35,6 +41,7 @@ constexpr int kRows = 8;                  // rows per lane: 8 x 4 direction bits
 constexpr int kStripe = kLanes * kRows;   // query rows per stripe
 constexpr int kLetters = 21;              // subject alphabet (dbdata codes)
 constexpr int kMatrixRows = 26;           // 25 query letters + the padding row (sw_set_matrix's internal form)
+constexpr int kTileWords = kRows * kLetters * kLanes;   // PSSM form: one stripe's rows in LDS, 43 008 bytes
 constexpr int32_t kNeg = -(1 << 30);      // E / F before any gap
 // The global passes clamp H at kFloor.  A path whose prefix went below it cannot climb back to a score >= 0 within
 // 2^20 query rows (int8 substitution scores), so no cell an optimal alignment uses ever differs from the exact DP.
@@ -51,6 +58,7 @@ __device__ __forceinline__ bool better(const Best& a, const Best& b) {
 }
 
 // one pass over rows x cols.  Row i (0-based) is query code q[dir * i], column j is subject letter s[dir * j].
+// PSSM form: row i is the PSSM row at q + dir * i * kLetters, and mrows is not used.
 struct Pass {
     const int8_t* q;
     const int8_t* s;
@@ -68,8 +76,38 @@ __device__ __forceinline__ int32_t shr1(int32_t lane0, int32_t src) {
 
 __device__ __forceinline__ int32_t imax(int32_t a, int32_t b) { return a > b ? a : b; }
 
+// PSSM form: rows [k * kStripe, k * kStripe + nrows) of the pass into the tile, the other rows of the tile zero.  The
+// stripe's rows are one contiguous piece of the row-major array (in kReverse it ends at the pass's row 0); the wave reads
+// it as aligned dwords, 64 consecutive ones per load, and scatters the four scores of each.  A dword that holds a byte of
+// the piece lies in memory the piece's pages cover, so the bytes around the piece are read but never used.
 template <int MODE>
-__device__ Best dp_pass(const Pass& ps, const int32_t* lds_m, const int lane) {
+__device__ __forceinline__ void load_tile(const Pass& ps, const int k, int32_t* tile, const int lane) {
+    constexpr int kTileBytes = kStripe * kLetters;
+    const int32_t left = ps.rows - k * kStripe;
+    const int32_t nrows = left < kStripe ? left : kStripe;
+    const int32_t nbytes = nrows * kLetters;
+    const int8_t* lo = MODE == kReverse ? ps.q - ((int64_t)k * kStripe + nrows - 1) * kLetters : ps.q + (int64_t)k * kStripe * kLetters;
+    const uintptr_t addr = reinterpret_cast<uintptr_t>(lo);
+    const int32_t shift = (int32_t)(addr & 3);
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(addr & ~uintptr_t(3));
+    for (int32_t w = lane; w < (kTileBytes + 3) / 4 + 1; w += kLanes) {
+        const int32_t e0 = 4 * w - shift;   // byte of the piece the dword starts with
+        const uint32_t v = e0 < nbytes ? words[w] : 0u;
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const int32_t e = e0 + b;
+            if (e < 0 || e >= kTileBytes) continue;
+            const int32_t m = e / kLetters, c = e - m * kLetters;
+            const bool valid = e < nbytes;
+            const int32_t n = (MODE == kReverse && valid) ? nrows - 1 - m : m;   // row of the stripe
+            tile[((n % kRows) * kLetters + c) * kLanes + n / kRows] = valid ? (int32_t)(int8_t)(v >> (8 * b)) : 0;
+        }
+    }
+}
+
+// lds_m: the letter form's substitution rows (kMatrixRows x kLetters), or the PSSM form's tile (kTileWords)
+template <int MODE, bool PSSM = false>
+__device__ Best dp_pass(const Pass& ps, int32_t* lds_m, const int lane) {
     constexpr bool kGlobal = MODE != kLocal;
     constexpr int dir = MODE == kReverse ? -1 : 1;
     const int32_t gop = ps.gop, gex = ps.gex;
@@ -84,15 +122,23 @@ __device__ Best dp_pass(const Pass& ps, const int32_t* lds_m, const int lane) {
     };
     Best best{kGlobal ? INT_MIN : 0, INT_MAX, INT_MAX};
     for (int k = 0; k < nst; k++) {
-        if (k) __syncthreads();   // the border lane 63 wrote is visible to lane 0
+        if (k) __syncthreads();   // the border lane 63 wrote is visible to lane 0 (PSSM form: and the tile is free)
+        if constexpr (PSSM) {
+            load_tile<MODE>(ps, k, lds_m, lane);
+            __syncthreads();      // the tile is complete
+        }
         const int32_t row0 = k * kStripe + lane * kRows;
         const int32_t nvalid = ps.rows - row0 < 0 ? 0 : (ps.rows - row0 > kRows ? kRows : ps.rows - row0);
         int32_t qo[kRows], Hl[kRows], E[kRows];
 #pragma unroll
         for (int r = 0; r < kRows; r++) {
-            int32_t c = r < nvalid ? ps.q[dir * (int64_t)(row0 + r)] : 0;
-            c = (unsigned)c < (unsigned)ps.mrows ? c : 0;
-            qo[r] = c * kLetters;
+            if constexpr (PSSM) {
+                qo[r] = r * kLetters * kLanes + lane;   // + letter * kLanes: the word of (row r of this lane, letter)
+            } else {
+                int32_t c = r < nvalid ? ps.q[dir * (int64_t)(row0 + r)] : 0;
+                c = (unsigned)c < (unsigned)ps.mrows ? c : 0;
+                qo[r] = c * kLetters;
+            }
             Hl[r] = edge(row0 + r + 1);
             E[r] = kNeg;
         }
@@ -113,6 +159,7 @@ __device__ Best dp_pass(const Pass& ps, const int32_t* lds_m, const int lane) {
                 const uint32_t w = *reinterpret_cast<const uint32_t*>(addr & ~uintptr_t(3));
                 const int32_t c = (int32_t)((w >> (8 * (addr & 3))) & 0xffu);
                 letter = c > kLetters - 1 ? kLetters - 1 : c;
+                if constexpr (PSSM) letter *= kLanes;   // travels down the lanes as the tile offset of its column
                 if (k == 0) {
                     bh = edge(t + 1);
                 } else {
@@ -177,6 +224,7 @@ __device__ Best dp_pass(const Pass& ps, const int32_t* lds_m, const int lane) {
     return best;
 }
 
+// PSSM form: `matrix` is the PSSM (qlen x kLetters, row-major), `query` the consensus codes or null, mrows is not used
 struct AlignParams {
     const int8_t* query;
     int32_t qlen;
@@ -202,10 +250,36 @@ __device__ __forceinline__ void load_matrix(const AlignParams& p, int32_t* lds_m
     __syncthreads();
 }
 
+// the LDS of a kernel and what fills it before the passes: the table (letter form) or nothing (the passes load the tile)
+template <bool PSSM>
+constexpr int kLdsWords = PSSM ? kTileWords : kMatrixRows * kLetters;
+
+template <bool PSSM>
+__device__ __forceinline__ void load_scores(const AlignParams& p, int32_t* lds_m) {
+    if constexpr (!PSSM) load_matrix(p, lds_m);
+}
+
+// row i of the query as a pass sees it
+template <bool PSSM>
+__device__ __forceinline__ const int8_t* query_row(const AlignParams& p, int32_t i) {
+    return PSSM ? p.matrix + (int64_t)i * kLetters : p.query + i;
+}
+
+// PSSM form: the consensus code of position i — the caller's, or the lowest code < 20 with the largest score
+__device__ __forceinline__ int32_t consensus_code(const AlignParams& p, int32_t i) {
+    if (p.query) return p.query[i];
+    const int8_t* row = p.matrix + (int64_t)i * kLetters;
+    int32_t best = 0;
+    for (int32_t c = 1; c < 20; c++)
+        if (row[c] > row[best]) best = c;
+    return best;
+}
+
 // (a): score, end, status
+template <bool PSSM>
 __global__ __launch_bounds__(kLanes) void align_end_kernel(AlignParams p) {
-    __shared__ int32_t lds_m[kMatrixRows * kLetters];
-    load_matrix(p, lds_m);
+    __shared__ int32_t lds_m[kLdsWords<PSSM>];
+    load_scores<PSSM>(p, lds_m);
     const int lane = threadIdx.x;
     const int32_t pair = p.first + blockIdx.x;
     const int32_t len = p.lengths[pair];
@@ -217,9 +291,9 @@ __global__ __launch_bounds__(kLanes) void align_end_kernel(AlignParams p) {
     Best b{0, -1, -1};
     if (len > 0 && p.qlen > 0) {
         char* slot = p.temp + (size_t)blockIdx.x * p.slot_bytes;
-        const Pass ps{p.query, p.chars + (p.offsets[pair] - p.offsets[0]), p.qlen, len, p.mrows, p.gop, p.gex,
+        const Pass ps{query_row<PSSM>(p, 0), p.chars + (p.offsets[pair] - p.offsets[0]), p.qlen, len, p.mrows, p.gop, p.gex,
                       reinterpret_cast<int2*>(slot), nullptr};
-        b = dp_pass<kLocal>(ps, lds_m, lane);
+        b = dp_pass<kLocal, PSSM>(ps, lds_m, lane);
     }
     if (lane == 0) {
         const int32_t S = b.v;
@@ -232,9 +306,10 @@ __global__ __launch_bounds__(kLanes) void align_end_kernel(AlignParams p) {
 }
 
 // (b): start
+template <bool PSSM>
 __global__ __launch_bounds__(kLanes) void align_start_kernel(AlignParams p) {
-    __shared__ int32_t lds_m[kMatrixRows * kLetters];
-    load_matrix(p, lds_m);
+    __shared__ int32_t lds_m[kLdsWords<PSSM>];
+    load_scores<PSSM>(p, lds_m);
     const int lane = threadIdx.x;
     const int32_t pair = p.first + blockIdx.x;
     sw_align_result* res = p.results + pair;
@@ -242,9 +317,9 @@ __global__ __launch_bounds__(kLanes) void align_start_kernel(AlignParams p) {
     if ((status != SW_ALIGN_OK && status != SW_ALIGN_SCORE_MISMATCH) || S <= 0) return;
     const int32_t qe = res->q_end - 1, se = res->s_end - 1;
     char* slot = p.temp + (size_t)blockIdx.x * p.slot_bytes;
-    const Pass ps{p.query + qe, p.chars + (p.offsets[pair] - p.offsets[0]) + se, qe + 1, se + 1, p.mrows, p.gop, p.gex,
+    const Pass ps{query_row<PSSM>(p, qe), p.chars + (p.offsets[pair] - p.offsets[0]) + se, qe + 1, se + 1, p.mrows, p.gop, p.gex,
                   reinterpret_cast<int2*>(slot), nullptr};
-    const Best b = dp_pass<kReverse>(ps, lds_m, lane);
+    const Best b = dp_pass<kReverse, PSSM>(ps, lds_m, lane);
     if (lane == 0) {
         res->q_begin = qe - b.i;
         res->s_begin = se - b.j;
@@ -252,9 +327,10 @@ __global__ __launch_bounds__(kLanes) void align_start_kernel(AlignParams p) {
 }
 
 // (c): direction bits of the rectangle, then lane 0 walks back from its far corner
+template <bool PSSM>
 __global__ __launch_bounds__(kLanes) void align_trace_kernel(AlignParams p) {
-    __shared__ int32_t lds_m[kMatrixRows * kLetters];
-    load_matrix(p, lds_m);
+    __shared__ int32_t lds_m[kLdsWords<PSSM>];
+    load_scores<PSSM>(p, lds_m);
     const int lane = threadIdx.x;
     const int32_t pair = p.first + blockIdx.x;
     sw_align_result* res = p.results + pair;
@@ -268,11 +344,11 @@ __global__ __launch_bounds__(kLanes) void align_trace_kernel(AlignParams p) {
         return;
     }
     char* slot = p.temp + (size_t)blockIdx.x * p.slot_bytes;
-    const int8_t* q = p.query + qs;
+    const int8_t* q = query_row<PSSM>(p, qs);
     const int8_t* s = p.chars + (p.offsets[pair] - p.offsets[0]) + ss;
     uint32_t* trace = reinterpret_cast<uint32_t*>(slot + p.border_bytes);
     const Pass ps{q, s, rows, cols, p.mrows, p.gop, p.gex, reinterpret_cast<int2*>(slot), trace};
-    dp_pass<kTrace>(ps, lds_m, lane);
+    dp_pass<kTrace, PSSM>(ps, lds_m, lane);
     __syncthreads();   // every lane's direction bits are visible to lane 0
     if (lane != 0) return;
     auto nib = [&](int32_t i, int32_t j) -> uint32_t {   // 0-based cell of the rectangle
@@ -302,8 +378,13 @@ __global__ __launch_bounds__(kLanes) void align_trace_kernel(AlignParams p) {
         const uint32_t d = nib(i - 1, j - 1);
         if (state == 0) {
             if ((d & 3u) == 0) {
-                const int8_t a = q[i - 1], b = s[j - 1];
-                if (a == b && a >= 0 && a < 20) { emit(SW_CIGAR_EQ); ids++; } else { emit(SW_CIGAR_X); mis++; }
+                if constexpr (PSSM) {
+                    const int32_t b = s[j - 1];
+                    if (b >= 0 && b < 20 && b == consensus_code(p, qs + i - 1)) { emit(SW_CIGAR_EQ); ids++; } else { emit(SW_CIGAR_X); mis++; }
+                } else {
+                    const int8_t a = q[i - 1], b = s[j - 1];
+                    if (a == b && a >= 0 && a < 20) { emit(SW_CIGAR_EQ); ids++; } else { emit(SW_CIGAR_X); mis++; }
+                }
                 i--;
                 j--;
             } else {
@@ -343,5 +424,6 @@ __global__ __launch_bounds__(kLanes) void align_trace_kernel(AlignParams p) {
     res->gap_columns = gcols;
     res->cigar_len = (int32_t)nruns;
 }
+
 
 }  // namespace swa

@@ -23,7 +23,8 @@ EXPORTS = ["swdrv_last_error", "swdrv_create", "swdrv_destroy", "swdrv_open_db",
            "swdrv_cached_chars", "swdrv_streamed_bytes", "swdrv_plan_residency", "swdrv_numa_node", "swdrv_device_of",
            "swdrv_bind_to_numa_node", "swdrv_device_numa_node", "swdrv_window_stats", "swdrv_service_launches",
            "swdrv_tail_overlaps", "swdrv_prefers_two_in_flight", "swdrv_pipeline_launches", "swdrv_handshake_active", "swdrv_preferred_in_flight",
-           "swdrv_latency_scans", "swdrv_plan_runs_mode", "swdrv_align_hits", "swdrv_scan_pssm", "swdrv_scan_submit_pssm"]
+           "swdrv_latency_scans", "swdrv_plan_runs_mode", "swdrv_align_hits", "swdrv_scan_pssm", "swdrv_scan_submit_pssm",
+           "swdrv_align_hits_pssm"]
 
 
 class DriverError(RuntimeError):
@@ -123,6 +124,15 @@ def _align_fn():
     if f.argtypes is None:
         vp = ctypes.c_void_p
         f.argtypes = [vp, ctypes.c_char_p, ctypes.c_int32, vp, vp, ctypes.c_int, vp, vp, ctypes.c_int64]
+    return f
+
+
+def _align_pssm_fn():
+    """swdrv_align_hits_pssm, bound on first use (like swdrv_align_hits: not in every build of this C ABI)"""
+    f = lib.swdrv_align_hits_pssm
+    if f.argtypes is None:
+        vp = ctypes.c_void_p
+        f.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_char_p, vp, vp, ctypes.c_int, vp, vp, ctypes.c_int64]
     return f
 
 
@@ -514,6 +524,29 @@ class Driver:
         cigar = np.zeros(max(cap, 1), dtype=np.uint32)
         _check(_align_fn()(self.handle, query_letters, len(query_letters), ids.ctypes.data, scores.ctypes.data, n,
                            res.ctypes.data, cigar.ctypes.data, cap))
+        cigars = [capi.cigar_string(cigar[int(r["cigar_offset"]):int(r["cigar_offset"]) + int(r["cigar_len"])]) for r in res]
+        return res, cigars
+
+    def align_hits_pssm(self, pssm, result, consensus=None):
+        """align_hits for the hits of a scan_pssm / submit_pssm result of `pssm` (swdrv_align_hits_pssm).  consensus: one
+        residue letter per position, which identities and '=' / 'X' are counted against (a non-standard letter is identical
+        to nothing); None: the best-scoring standard residue of every row (pssm.consensus_of).  Returns what align_hits returns."""
+        from . import capi, pssm as _pssm
+        m = _pssm.as_pssm(pssm)
+        qlen = m.shape[0]
+        if consensus is not None:
+            if isinstance(consensus, str):
+                consensus = consensus.encode()
+            if len(consensus) != qlen:
+                raise ValueError("consensus has %d residues, the PSSM %d rows" % (len(consensus), qlen))
+        ids = np.ascontiguousarray(result["ids"], dtype=np.int64)
+        scores = np.ascontiguousarray(result["scores"], dtype=np.int32)
+        n = len(ids)
+        res = np.zeros(n, dtype=capi.align_result_dtype())
+        cap = sum(qlen + self.reference_length(int(i)) for i in ids)
+        cigar = np.zeros(max(cap, 1), dtype=np.uint32)
+        _check(_align_pssm_fn()(self.handle, m.ctypes.data, qlen, consensus, ids.ctypes.data, scores.ctypes.data, n,
+                                res.ctypes.data, cigar.ctypes.data, cap))
         cigars = [capi.cigar_string(cigar[int(r["cigar_offset"]):int(r["cigar_offset"]) + int(r["cigar_len"])]) for r in res]
         return res, cigars
 

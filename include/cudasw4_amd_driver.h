@@ -73,7 +73,7 @@ int swdrv_in_flight(swdrv* d);
  * int8, row i = query position i, column c = dbdata subject code c (0..19 = ARNDCQEGHILKMFPSTWYV, 20 = other / padding:
  * negative in every row).  The driver's matrix is not used; its gap scores, shards, residency, streaming and merge are, and
  * the results have the layout of swdrv_scan's.  swdrv_scan_submit_pssm pairs with swdrv_scan_collect, so a PSSM query and
- * a letter query can be in flight together.  swdrv_align_hits does not apply to the hits of a PSSM query. */
+ * a letter query can be in flight together.  The hits of a PSSM query are aligned with swdrv_align_hits_pssm. */
 int swdrv_scan_pssm(swdrv* d, const int8_t* pssm, int32_t qlen, int32_t* scores, int64_t* ids, int cap,
                     int* nres, int* num_overflows, double* seconds, double* gcups);
 int swdrv_scan_submit_pssm(swdrv* d, const int8_t* pssm, int32_t qlen);
@@ -183,6 +183,12 @@ int swdrv_reference_header(swdrv* d, int64_t id, char* buf, int cap);
  * budget of one pair follows max_temp_bytes: pairs whose rectangle is over it get SW_ALIGN_NO_TRACE (coordinates only). */
 int swdrv_align_hits(swdrv* d, const char* query, int32_t qlen, const int64_t* ids, const int32_t* scores, int n,
                      sw_align_result* results, uint32_t* cigar, int64_t cigar_cap);
+/* The same for the hits of a PSSM query (sw_align_hits_pssm, include/cudasw4_amd_pssm.h).  pssm: the qlen x 21 int8 scores the
+ * hits were scanned with (host).  consensus: qlen residue letters that identities and the CIGAR's '=' / 'X' are counted
+ * against (a non-standard letter, '*' or '-' is identical to nothing), or NULL: the best-scoring standard residue of
+ * every row, the first of equals.  Gap scores, trace budget, outputs and errors as above; the driver's matrix is not used. */
+int swdrv_align_hits_pssm(swdrv* d, const int8_t* pssm, int32_t qlen, const char* consensus, const int64_t* ids,
+                          const int32_t* scores, int n, sw_align_result* results, uint32_t* cigar, int64_t cigar_cap);
 
 /* ---- input helpers (no GPU needed): what `align` does to its inputs before the scan ---- */
 

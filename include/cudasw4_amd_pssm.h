@@ -33,11 +33,23 @@ extern "C" {
  * sw_query_length) describe it — until the next sw_set_query (back to letters) or sw_set_query_pssm.  Bounds that a
  * letter query derives from the largest entry of the substitution table (the int32 kind served in fp32 lanes, the
  * overlap of windows) are derived from the largest entry of the PSSM.
- * sw_align_hits is not affected: it takes its query as an argument and scores with the context's matrix. */
+ * sw_align_hits is not affected: it takes its query as an argument and scores with the context's matrix.  The hits of a
+ * PSSM query are aligned with sw_align_hits_pssm below, which takes the PSSM as an argument in the same way. */
 int sw_set_query_pssm(sw_ctx* ctx, const int8_t* pssm_host, int32_t qlen, void* stream);
 
 /* 1 when the context's current query is a PSSM, 0 for a letter query or none. */
 int sw_query_is_pssm(const sw_ctx* ctx);
+
+/* sw_align_hits with a PSSM as the query.  pssm: DEVICE, a->qlen x SW_PSSM_COLUMNS int8 row-major (NOT the context's current
+ * query).  a->query: DEVICE consensus codes, one per position, or NULL (argmax consensus).  Needs no sw_set_matrix.
+ * Everything else in sw_align_args, the statuses, scratch rule, chunking and phase events are those of sw_align_hits.
+ *   Score: pssm[i][s_j] takes the place of matrix[query[i]][s_j] in all three passes (subject codes above 20 count as
+ *   20); the tie rules of the end, the start and the traceback are unchanged.
+ *   Identity: an aligned pair at query position i is SW_CIGAR_EQ (and counted in `identities`) when the subject code is
+ *   below 20 and equals the consensus code of position i, else SW_CIGAR_X.  Consensus codes of 20 and above are identical
+ *   to nothing.  Without a consensus, position i has the lowest code c < 20 with the largest pssm[i][c].
+ *   CONTRACT: column 20 of every row negative, as for the PSSM of a scan; the rows are read as they are. */
+int sw_align_hits_pssm(sw_ctx* ctx, const sw_align_args* a, const int8_t* pssm);
 
 #ifdef __cplusplus
 }
