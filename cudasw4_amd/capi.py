@@ -31,7 +31,7 @@ EXPORTS = ["sw_batch_create", "sw_batch_destroy", "sw_scan_batch", "sw_batch_joi
            "sw_rescore_service_temp_bytes", "sw_streams_run_concurrently", "sw_set_dry_signal", "sw_set_dirty_counter", "sw_set_grid_reserve",
            "sw_set_long16_min", "sw_scan_rows_pipelined",
            "sw_scan_rows_pipelined_temp_bytes", "sw_probe_handshake", "sw_launch_vgpr_slot",
-           "sw_set_rows_pipeline_slot", "sw_rescore_overflow_pipelined", "sw_rescore_overflow_pipelined_temp_bytes", "sw_measure_valu_rate",
+           "sw_set_rows_pipeline_slot", "sw_packed_launch_falls_back", "sw_scan_partition_counted", "sw_rescore_overflow_pipelined", "sw_rescore_overflow_pipelined_temp_bytes", "sw_measure_valu_rate",
            "sw_align_hits"]
 # ... and include/cudasw4_amd_pssm.h (profile search: a position-specific scoring matrix as the query)
 PSSM_EXPORTS = ["sw_set_query_pssm", "sw_query_is_pssm", "sw_align_hits_pssm"]

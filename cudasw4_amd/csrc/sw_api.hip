@@ -1363,6 +1363,39 @@ int sw_scan_partition(sw_ctx* ctx, int kind, int part_id, const int8_t* chars, c
                        static_cast<hipStream_t>(stream));
 }
 
+int sw_packed_launch_falls_back(sw_ctx* ctx, int kind, int part_id, int32_t n, int32_t max_subject_len, int gop, int gex) {
+    if (!ctx || !kind_launch(kind) || !kind_packed(kind) || !ctx->have_query || part_id < 0 || part_id >= SW_NUM_LENGTH_PARTITIONS) return 0;
+    const int lanes = lanes_for_partition(ctx, kind, part_id, n, max_subject_len);
+    return offs_possible(ctx, kind, lanes, max_subject_len, gop, gex, 1, nullptr) ? 0 : 1;
+}
+
+namespace {
+__global__ void add_counter_kernel(const int32_t* src, int32_t* dst) {
+    if (*src) atomicAdd(dst, *src);
+}
+}  // namespace
+
+int sw_scan_partition_counted(sw_ctx* ctx, int kind, int part_id, const int8_t* chars, const uint64_t* offsets,
+                              const int32_t* lengths, int32_t first_pos, int32_t n, int32_t max_subject_len, int gop, int gex,
+                              float* scores, int32_t* ids, int64_t id_offset, int32_t packed_limit, int32_t* over_limit_count,
+                              int32_t* over_limit_total, void* temp, size_t temp_bytes, void* stream) {
+    if (!ctx) return fail(SW_ERR_INVALID, "null context");
+    if (!over_limit_count || !sw_packed_launch_falls_back(ctx, kind, part_id, n, max_subject_len, gop, gex)) {
+        ctx->start_signal = nullptr;   // one-shot: a call that fails cancels what was armed for it
+        ctx->dry_signal = nullptr;
+        return fail(SW_ERR_INVALID, "sw_scan_partition_counted: not a packed launch that falls back to its 32-bit kind, or no counter");
+    }
+    kind = effective_kind_of(ctx, packed_fallback_kind(kind), max_subject_len);
+    const int lanes = lanes_for_partition(ctx, kind, part_id, n, max_subject_len);
+    const int rc = scan_common(ctx, kind, lanes, chars, offsets, lengths, nullptr, nullptr, first_pos, n, max_subject_len, gop, gex,
+                               scores, ids, id_offset, nullptr, nullptr, 0, temp, temp_bytes, static_cast<hipStream_t>(stream),
+                               over_limit_count, packed_limit);
+    if (rc != SW_OK || n == 0 || !over_limit_total) return rc;
+    hipLaunchKernelGGL(add_counter_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), over_limit_count, over_limit_total);
+    SW_HIP(hipGetLastError());
+    return SW_OK;
+}
+
 int sw_rescore_overflow(sw_ctx* ctx, int kind, const int32_t* ovf_pos, const int32_t* ovf_count, int32_t max_count,
                         const int8_t* chars, const uint64_t* offsets, const int32_t* lengths, int32_t max_subject_len,
                         int gop, int gex, float* scores, int32_t* ids, int64_t id_offset, void* temp,

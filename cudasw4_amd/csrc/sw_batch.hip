@@ -32,6 +32,17 @@
 #include "../../include/cudasw4_amd_engine.h"
 #include "sw_internal.hpp"
 
+// The two entry points for packed launches that fall back to 32 bits are OPTIONAL for the engine: a library of this C ABI
+// that does not have them (a stand-in for the kernel library, written before they existed) leaves the references null, and
+// the engine then treats every packed run as before.
+extern "C" {
+int sw_packed_launch_falls_back(sw_ctx* ctx, int kind, int part_id, int32_t n, int32_t max_subject_len, int gop, int gex) __attribute__((weak));
+int sw_scan_partition_counted(sw_ctx* ctx, int kind, int part_id, const int8_t* chars, const uint64_t* offsets,
+                              const int32_t* lengths, int32_t first_pos, int32_t n, int32_t max_subject_len, int gop, int gex,
+                              float* scores, int32_t* ids, int64_t id_offset, int32_t packed_limit, int32_t* over_limit_count,
+                              int32_t* over_limit_total, void* temp, size_t temp_bytes, void* stream) __attribute__((weak));
+}
+
 namespace {
 
 constexpr int kParts = SW_NUM_LENGTH_PARTITIONS;
@@ -369,6 +380,7 @@ struct BatchJob {
     std::vector<Run> runs;
     size_t mainIdx = 0;
     std::vector<int> ovfList;
+    std::vector<char> fellBack;   // packed runs that sw_scan_partition serves in 32 bits (sw_packed_launch_falls_back): no list, no re-score
     // launches
     int recUsed = 0;
     int auxNext = 0;
@@ -481,12 +493,18 @@ struct BatchJob {
         for (size_t i = 0; i < runs.size(); i++)
             if (packed(runs[i].kind)) ovfList[i] = std::min(numLists++, kLists - 1);
         shareLast = numLists > kLists;   // (never with the reference's partitions: at most three runs per batch)
+        // gap scores that leave a packed kind no frame period (fp16 with |gex| > 12): the launcher serves the run in 32 bits and
+        // flags nothing, so the run has nothing to re-score and its share of the overflow statistic comes from the launch itself
+        fellBack.assign(runs.size(), 0);
+        for (size_t i = 0; i < runs.size(); i++)
+            if (sw_packed_launch_falls_back && sw_scan_partition_counted && ovfList[i] >= 0 && !(shareLast && ovfList[i] == kLists - 1))
+                fellBack[i] = sw_packed_launch_falls_back(ctx, runs[i].kind, runs[i].part_id, runs[i].end - runs[i].begin, runs[i].maxlen, gop, gex) == 1;
 
         // ---- re-score service for the bulk run's overflow list: a few workgroups that re-score the list while the bulk launch
         // fills it (sw_rescore_service); worth it where one re-scored subject takes about as long as a launch does at all
         const bool serviceWanted = b->svcForce >= 0 ? b->svcForce == 1 : b->quietScans < 3;
         useService = b->handshake && b->svc && b->svcConcurrent && a->allow_service && serviceWanted && !runs.empty() &&
-                                packed(runs[mainIdx].kind) && double(qlen) * double(runs[mainIdx].maxlen) >= 5e5;
+                                packed(runs[mainIdx].kind) && !fellBack[mainIdx] && double(qlen) * double(runs[mainIdx].maxlen) >= 5e5;
         return SW_OK;
     }
 
@@ -513,9 +531,15 @@ struct BatchJob {
         sw_launch_record* rec = nullptr;
         SWB_OK(rec_begin(stream, tslot == workTemp, r.kind, r.part_id, r.begin, r.end, r.maxlen, false, &rec));
         const bool pk = ovfList[ri] >= 0;
-        SWB_OK(sw_scan_partition(ctx, r.kind, r.part_id, a->chars, a->offsets, a->lengths, r.begin, cnt, r.maxlen, gop, gex, a->scores, a->ids,
-                                 a->id_offset, pk ? a->ovf_pos + r.begin : nullptr, pk ? counters + SW_BATCH_CNT_LIST0 + ovfList[ri] : nullptr,
-                                 pk ? 1 : 0, temp, b->tempBytes[tslot], stream));
+        if (fellBack[ri]) {   // the run's list counter takes the subjects at or above the packed limit: scored in 32 bits, like the listed ones
+            SWB_OK(sw_scan_partition_counted(ctx, r.kind, r.part_id, a->chars, a->offsets, a->lengths, r.begin, cnt, r.maxlen, gop, gex, a->scores, a->ids,
+                                             a->id_offset, r.kind == SW_KIND_F16X2 ? SW_MAX_ACC_F16 : SW_MAX_ACC_I16,
+                                             counters + SW_BATCH_CNT_LIST0 + ovfList[ri], counters + SW_BATCH_CNT_OVERFLOWS, temp, b->tempBytes[tslot], stream));
+        } else {
+            SWB_OK(sw_scan_partition(ctx, r.kind, r.part_id, a->chars, a->offsets, a->lengths, r.begin, cnt, r.maxlen, gop, gex, a->scores, a->ids,
+                                     a->id_offset, pk ? a->ovf_pos + r.begin : nullptr, pk ? counters + SW_BATCH_CNT_LIST0 + ovfList[ri] : nullptr,
+                                     pk ? 1 : 0, temp, b->tempBytes[tslot], stream));
+        }
         return rec_end(rec, stream);
     }
     // rough clocks of a side launch of long subjects and of the bulk launch beside it
@@ -632,7 +656,7 @@ struct BatchJob {
         return SW_OK;
     }
     int rescore(size_t ri, hipStream_t stream, int tslot) {   // cudasw4.cuh:2134-2169
-        if (ovfList[ri] < 0) return SW_OK;
+        if (ovfList[ri] < 0 || fellBack[ri]) return SW_OK;
         const Run& r = runs[ri];
         const int32_t cnt = r.end - r.begin;
         const int okind = a->kinds[3];

@@ -156,6 +156,23 @@ int32_t sw_window_overlap(sw_ctx* ctx, int gop, int gex);
 int sw_reduce_windows(sw_ctx* ctx, const float* win_scores, const int32_t* win_first, const int32_t* real_pos, int32_t n_real,
                       float* scores, int32_t* ids, int64_t id_offset, void* stream);
 
+/* Packed launches that fall back to 32 bits.  Gap scores that leave the column-offset recurrence of a packed kind no frame
+ * period (fp16 with |gex| > 12) send sw_scan_partition to the kind's 32-bit counterpart: every score is exact, nothing is
+ * flagged, the overflow list stays empty — and a caller that keeps the reference's "num overflows" statistic from its
+ * re-score launches (sw_rescore_overflow_stat) would count nothing for that launch.
+ *   sw_packed_launch_falls_back  1 when sw_scan_partition with these arguments (CURRENT query, an overflow list) would
+ *                                fall back, 0 otherwise (also for a 32-bit kind)
+ *   sw_scan_partition_counted    sw_scan_partition for such a launch (SW_ERR_INVALID for any other) that keeps the
+ *                                statistic itself: *over_limit_count (DEVICE int32, zero before the launch and written by no
+ *                                one else: the slot of the list the launch does not fill) += 1 per subject whose score is
+ *                                >= packed_limit; behind the launch *over_limit_total (DEVICE, optional, may be shared
+ *                                between launches) += *over_limit_count.  There is no list and nothing to re-score. */
+int sw_packed_launch_falls_back(sw_ctx* ctx, int kind, int part_id, int32_t n, int32_t max_subject_len, int gop, int gex);
+int sw_scan_partition_counted(sw_ctx* ctx, int kind, int part_id, const int8_t* chars, const uint64_t* offsets,
+                              const int32_t* lengths, int32_t first_pos, int32_t n, int32_t max_subject_len, int gop, int gex,
+                              float* scores, int32_t* ids, int64_t id_offset, int32_t packed_limit, int32_t* over_limit_count,
+                              int32_t* over_limit_total, void* temp, size_t temp_bytes, void* stream);
+
 /* What sw_scan_batch WOULD launch for these arguments with the context's current query, as text (debugging a binding; the
  * CPU tests of the planner): "pipeline p35 [b,e) maxlen m; bulk kind k p33 [b,e) maxlen m list 0; side ...; service 0; split34 0".
  * No buffer of `a` is touched, nothing is enqueued. */

@@ -75,7 +75,7 @@ def rescore(pssm, s, gop, gex, r, words):
                 i += 1
                 j += 1
         else:
-            total += gop + (n - 1) * gex
+            total += gop + (n - 1) * max(gop, gex)   # (gop > gex: the recurrence opens anew in every column of the run)
             if op == 1:
                 i += n
             else:

@@ -484,7 +484,7 @@ def test_align_ref_compat_switch(tmp_path):
 
     def run(extra):
         of = str(tmp_path / "o.tsv")
-        p = subprocess.run([driver.ALIGN, "--query", FASTA, "--db", GOLDEN_DB, "--top", "20", "--tsv", "--of", of] + extra,
+        p = subprocess.run(["timeout", "-k", "10", "240", driver.ALIGN, "--query", FASTA, "--db", GOLDEN_DB, "--top", "20", "--tsv", "--of", of] + extra,
                            capture_output=True, text=True)
         assert p.returncode == 0, p.stderr
         rows = [l.split("\t") for l in open(of).read().splitlines()[1:]]
@@ -492,6 +492,14 @@ def test_align_ref_compat_switch(tmp_path):
         for r in rows:
             sc[int(r[0]), int(r[7])] = int(r[4])
         return sc, p.stdout
+
+    def printed_gaps(out):
+        """the gap scores of a run's options dump"""
+        opts = dict(l.split(": ", 1) for l in out.splitlines() if l.startswith(("gop: ", "gex: ")))
+        return int(opts["gop"]), int(opts["gex"])
+
+    def oracle(mat, gop, gex):
+        return np.array([O.scan(q, chars, offsets, lengths, m21=O.blosum21(mat), gop=gop, gex=gex, simd=True) for q in queries])
 
     for mat in (45, 80):
         want = np.array([O.scan(q, chars, offsets, lengths, m21=O.blosum21(mat), gop=-11, gex=-1, simd=True) for q in queries])
@@ -501,6 +509,14 @@ def test_align_ref_compat_switch(tmp_path):
         assert (compat2 == want).all()
         native, out = run(["--mat", "blosum%d" % mat])
         assert "refCompat" not in out and (native != want).any()
+        # ... and what it prints without the switch are the scores under the gap scores it says it applies
+        gop, gex = printed_gaps(out)
+        assert (gop, gex) != (-11, -1) and "blosum: blosum%d" % mat in out
+        assert (native == oracle(mat, gop, gex)).all(), (mat, gop, gex, np.argwhere(native != oracle(mat, gop, gex))[:5])
+    # explicit gap scores reach the scan
+    explicit, out = run(["--gop", "-5", "--gex", "-3"])
+    assert printed_gaps(out) == (-5, -3) and "refCompat" not in out
+    assert (explicit == oracle(62, -5, -3)).all(), np.argwhere(explicit != oracle(62, -5, -3))[:5]
     # the environment switch does the same
     env = dict(os.environ, CUDASW4_AMD_REF_COMPAT="1")
     of = str(tmp_path / "e.tsv")
