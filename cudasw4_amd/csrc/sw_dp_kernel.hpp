@@ -23,8 +23,9 @@
 //   * the recurrence runs in a column-offset frame (dp_step<OFFS>): every value of subject column j is kept raised by
 //     |gex| * (j mod K + LANES), which takes the "+ gex" out of the horizontal gap state, and lane-local row r by a
 //     further |gex| * (r mod P) (row classes), which takes it out of the vertical gap state except where the class
-//     wraps: 5.8 instead of 8.5 instructions per cell pair; the plain form remains for gap-extension scores too
-//     large for any K.  The packed sw_scan_kernel runs it in the UNIFORM frame instead: a cell of step t of stripe s is
+//     wraps: 5.8 instead of 8.5 instructions per cell pair; the plain form remains in the 32-bit kinds only, for
+//     gap-extension scores too large for any K (a packed launch that cannot run the column-offset form is served by its
+//     32-bit kind: sw_launch.hpp).  The packed sw_scan_kernel runs it in the UNIFORM frame instead: a cell of step t of stripe s is
 //     raised by |gex| * ((t + LANES*s) mod K + 1 + class), the same zero levels in every lane of the wave — held in scalar
 //     registers, the frame lowered by every lane in the same step (sw_scan_kernel explains the constants); the streamed
 //     kernels keep the column frame;
@@ -112,9 +113,6 @@ __device__ __forceinline__ u32 prev_lane(u32 headval, u32 src, bool head) {
 // (E' = max(E,0), F' = max(F,0)), which leaves H = max(diag+s, E', F') unchanged and makes the
 // explicit max(.,0) of the reference recurrence (half2_kernels.cuh:176) free.
 // ------------------------------------------------------------------------------------------------
-#ifndef SWK_F32_WINDOW
-#define SWK_F32_WINDOW 0
-#endif
 template <int KIND>
 struct Arith;
 
@@ -154,10 +152,7 @@ struct Arith<I16X2> {
     static __device__ __forceinline__ u32 gap(u32 a, u32 g) {
         return __builtin_bit_cast(u32, (u16x2)(__builtin_bit_cast(u16x2, a) - __builtin_bit_cast(u16x2, g)));
     }
-    static __device__ __forceinline__ u32 gap_state(u32 ext, u32 open) { return max3(ext, open, kZero); }
     static __device__ __forceinline__ u32 fold2(u32 m, u32 a, u32 b) { return max3(m, a, b); }
-    static __device__ __forceinline__ int score_lo(u32 v) { return (int)(v & 0xffffu) - kBias; }
-    static __device__ __forceinline__ int score_hi(u32 v) { return (int)(v >> 16) - kBias; }
     // column-offset recurrence (dp_step<OFFS>): the zero level of column offset k, +a, star -> true values
     static __host__ __device__ u32 zero_at(int a, int k) { u32 z = (u32)(kBias + a * k) & 0xffffu; return z | (z << 16); }
     static __host__ __device__ u32 pos_word(int a) { u32 m = (u32)a & 0xffffu; return m | (m << 16); }
@@ -215,10 +210,7 @@ struct Arith<F16X2> {
     }
     static __device__ __forceinline__ u32 cell_h(u32 t, u32 e, u32 f) { return max3(t, e, f); }
     static __device__ __forceinline__ u32 gap(u32 a, u32 g) { return add(a, g); }  // not clamped yet
-    static __device__ __forceinline__ u32 gap_state(u32 ext, u32 open) { return max3(ext, open, 0u); }
     static __device__ __forceinline__ u32 fold2(u32 m, u32 a, u32 b) { return max3(m, a, b); }  // one v_pk_maximum3_f16 per two rows
-    static __device__ __forceinline__ int score_lo(u32 v) { return (int)(float)__builtin_bit_cast(f16x2, v).x; }
-    static __device__ __forceinline__ int score_hi(u32 v) { return (int)(float)__builtin_bit_cast(f16x2, v).y; }
     static __host__ __device__ u32 zero_at(int a, int k) { u32 h = half_bits(a * k); return h | (h << 16); }
     static __host__ __device__ u32 pos_word(int a) { u32 h = half_bits(a); return h | (h << 16); }
     // the zero level v (|v| <= 2048: exact) in both halves, by the hardware conversion
@@ -231,8 +223,8 @@ struct Arith<F16X2> {
     }
     static __device__ __forceinline__ u32 lower(u32 a, u32 w) { return add(a, w); }  // w = encode_gap(-a*K)
     static __device__ __forceinline__ u32 true_max(u32 a, u32 b) { return max2(a, b); }
-    static __device__ __forceinline__ int true_lo(u32 v) { return score_lo(v); }
-    static __device__ __forceinline__ int true_hi(u32 v) { return score_hi(v); }
+    static __device__ __forceinline__ int true_lo(u32 v) { return (int)(float)__builtin_bit_cast(f16x2, v).x; }
+    static __device__ __forceinline__ int true_hi(u32 v) { return (int)(float)__builtin_bit_cast(f16x2, v).y; }
     // wide profile words (score, 1.0): one v_pk_fma_f16 with op_sel (exact: a product with 1.0, one rounding of an integer sum)
     static constexpr u32 kOne = 0x3c00u;
     static __device__ __forceinline__ u32 add_pair(u32 wa, u32 wb, u32 c) {
@@ -273,7 +265,6 @@ struct Arith<I32> {
     static __device__ __forceinline__ u32 gap_state(u32 ext, u32 open) { return max3_zero(ext, open); }
     static __device__ __forceinline__ u32 fold2(u32 m, u32 a, u32 b) { return max3(m, a, b); }
     static __device__ __forceinline__ int score_lo(u32 v) { return (int)v; }
-    static __device__ __forceinline__ int score_hi(u32) { return 0; }
     static __host__ __device__ u32 zero_at(int a, int k) { return (u32)(a * k); }
     static __host__ __device__ u32 pos_word(int a) { return (u32)a; }
     static __device__ __forceinline__ u32 true_of(u32 m, u32 z) { return m - z; }
@@ -289,7 +280,7 @@ struct Arith<F32> {
     static constexpr int kLimit = 0x7fffffff;
     // the fp32 kernels (168 VGPRs for three waves per SIMD) spill in their loops with the 7 extra window registers
     // (7.9 -> 1.6 TCUPS): they add a per step to P zero levels and P maxima instead
-    static constexpr bool kWindow = SWK_F32_WINDOW != 0;
+    static constexpr bool kWindow = false;
     static constexpr u32 kZero = 0u;
     static __host__ __device__ u32 encode_gap(int g) { return __builtin_bit_cast(u32, (float)g); }
     static __host__ __device__ u32 encode_score(int s) { return __builtin_bit_cast(u32, (float)s); }
@@ -303,7 +294,6 @@ struct Arith<F32> {
     static __device__ __forceinline__ u32 gap_state(u32 ext, u32 open) { return u(__builtin_fmaxf(__builtin_fmaxf(f(ext), f(open)), 0.0f)); }
     static __device__ __forceinline__ u32 fold2(u32 m, u32 a, u32 b) { return u(__builtin_fmaxf(__builtin_fmaxf(f(m), f(a)), f(b))); }  // v_max3_f32
     static __device__ __forceinline__ int score_lo(u32 v) { return (int)f(v); }
-    static __device__ __forceinline__ int score_hi(u32) { return 0; }
     static __host__ __device__ u32 zero_at(int a, int k) { return __builtin_bit_cast(u32, (float)(a * k)); }
     static __host__ __device__ u32 pos_word(int a) { return __builtin_bit_cast(u32, (float)a); }
     static __device__ __forceinline__ u32 true_of(u32 m, u32 z) { return u(f(m) - f(z)); }
@@ -508,12 +498,6 @@ __device__ __forceinline__ void lds_read_words(u32 (&dst)[NW], const unsigned ch
 // (sw_api.hip: plan_query; peak benchmark 11.53 -> 11.67 TCUPS).  0: none.
 #define SWK_WAVES3_MAX_R_MULTI 32
 #endif
-#ifndef SWK_MULTI_SCALAR_LOOP
-// multi-stripe kernels: the quad counters in scalar registers too (wave-uniform by construction).  Rounds 1-3 kept them in
-// vector registers (the scalar form measured 1 % slower then); with the block loop of the LDS border rings the scalar
-// form is the faster one (11.39 -> 11.44 TCUPS) and frees registers
-#define SWK_MULTI_SCALAR_LOOP 1
-#endif
 #ifndef SWK_WAVES4_MAX_R
 #define SWK_WAVES4_MAX_R 22   // ... and up to this many to 128 VGPRs = four waves per SIMD (+1 % at R = 17..22, -0.4 % at 24)
 #endif
@@ -540,6 +524,9 @@ constexpr int frame_classes(bool packed, int R, int lanes, bool multi, bool unif
     while (P > 1 && 2 * P > R) P--;  // at least two rows per class, so that the running maximum still folds two rows per max3
     return P;
 }
+
+// Wide kernels: how many rows the diagonal terms run ahead of the chain in dp_step (8 and 16 measured within 0.1 %)
+constexpr int kLookahead = 12;
 
 // the words of two letters, chunk by chunk (A's chunk k, B's chunk k, ...): LDS answers in order, so the first rows'
 // score words arrive after two reads instead of after all of A's
@@ -617,11 +604,7 @@ __device__ __forceinline__ void dp_step(StripeState<KIND, R, P>& st, const unsig
     constexpr u32 kSel = 0x0c0c000cu | ((u32)BYTE << 8);  // letter byte BYTE -> bits 15:8
     constexpr int kPostShift = G::kLetterShift - 8;        // row offset = byte << kLetterShift
 
-    // 32-bit kinds, column-offset form: progressive LDS reads like the wide kernels (SWK_PROG_SCALAR=0: all at the top)
-#ifndef SWK_PROG_SCALAR
-#define SWK_PROG_SCALAR 1
-#endif
-    constexpr bool kProgScalar = SWK_PROG_SCALAR != 0;
+    static_assert(!A::kPacked || OFFS, "packed kinds run the column-offset recurrence only");
     // subject letter(s): shift along the group, lane 0 takes the next letter of its subject
     u32 wa[G::NW];
     u32 wb[G::NW];
@@ -630,11 +613,11 @@ __device__ __forceinline__ void dp_step(StripeState<KIND, R, P>& st, const unsig
         constexpr u32 kSel2 = ((u32)(4 + BYTE) << 24) | 0x000c000cu | ((u32)BYTE << 8);  // B's byte -> 31:24, A's -> 15:8
         const u32 inj = __builtin_amdgcn_perm(lettersB, lettersA, kSel2);
         st.yA = prev_lane<LANES, false>(inj, st.yA, head) + step2;
-        if constexpr (!OFFS) lds_read_words2<G::NW, G::kChunkRowBytes>(wa, wb, tile + (st.yA & 0xffffu), tile + (st.yA >> 16));
     } else {
         const u32 injA = __builtin_amdgcn_perm(0u, lettersA, kSel) << kPostShift;
         st.yA = prev_lane<LANES, false>(injA, st.yA, head) + step1;
-        if constexpr (A::kPacked || !OFFS || !kProgScalar) lds_read_words<G::NW, G::kChunkRowBytes>(wa, tile + st.yA);
+        // (32-bit kinds, column-offset form: progressive reads like the wide kernels, issued below)
+        if constexpr (A::kPacked || !OFFS) lds_read_words<G::NW, G::kChunkRowBytes>(wa, tile + st.yA);
         if constexpr (A::kPacked) {
             const u32 injB = __builtin_amdgcn_perm(0u, lettersB, kSel) << kPostShift;
             st.yB = prev_lane<LANES, false>(injB, st.yB, head) + step1;
@@ -688,10 +671,7 @@ __device__ __forceinline__ void dp_step(StripeState<KIND, R, P>& st, const unsig
         // Wide words: the diagonal terms run kAhead rows ahead of the chain and the scheduler may only reorder within
         // four rows (it would otherwise compute all of them first, in register order, and so wait for the LAST LDS
         // chunk at the top of the step): a row needs its score words only when the chain is kAhead rows away.
-#ifndef SWK_LOOKAHEAD
-#define SWK_LOOKAHEAD 12
-#endif
-        constexpr int kAhead = G::kWide ? (SWK_LOOKAHEAD < R ? SWK_LOOKAHEAD : R) : 1;
+        constexpr int kAhead = G::kWide ? (kLookahead < R ? kLookahead : R) : 1;
         // ... and the LDS reads themselves are issued progressively: the chunks the first kAhead + 4 rows need at the top
         // of the step, chunk k + kChunks0 when the chain reaches row 4k — a few chunks are in flight instead of all
         // (2R registers), which is what lets R go up to 48
@@ -710,7 +690,7 @@ __device__ __forceinline__ void dp_step(StripeState<KIND, R, P>& st, const unsig
 #pragma unroll
             for (int r = 0; r < kAhead; r++) tq[r] = A::add_pair(wa[r], wb[r], r == 0 ? diag : st.H[r - 1]);
         }
-        constexpr bool kProg1 = !A::kPacked && kProgScalar;
+        constexpr bool kProg1 = !A::kPacked;
         // the score of row r + 2 is picked up when the chain is at row r: rows 0..7 at the top of the step when the chunks
         // are full ones, the chunk after those when the chain reaches a chunk's first row
         constexpr int kChunks0S = kProg1 ? CH::lead_for(2, 6) : 1;
@@ -763,49 +743,38 @@ __device__ __forceinline__ void dp_step(StripeState<KIND, R, P>& st, const unsig
         }
         st.Hlast = st.H[R - 1];
         st.Fout = F;
-        return;
-    }
-
-    // row above the lane's first row: from the neighbouring lane, or from the stripe border
-    u32 upH, F;
-    if constexpr (MULTI) {
-        upH = prev_lane<LANES, false>(inH, st.Hlast, head);  // lane 0 keeps `old` == the border value
-        F = prev_lane<LANES, false>(inF, st.Fout, head);
-    } else if constexpr (A::kZero == 0u) {
-        upH = prev_lane<LANES, true>(0u, st.Hlast, head);  // bound_ctrl zero fill == the local-alignment boundary
-        F = prev_lane<LANES, true>(0u, st.Fout, head);
     } else {
-        upH = prev_lane<LANES, false>(A::kZero, st.Hlast, head);
-        F = prev_lane<LANES, false>(A::kZero, st.Fout, head);
-    }
-    u32 diag = st.upH_prev;
-    st.upH_prev = upH;
-
-    u32 maxv = st.maxv[0];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        u32 t;
-        if constexpr (G::kWide) {
-            t = A::add_pair(wa[r], wb[r], diag);
-        } else if constexpr (A::kPacked) {
-            // (score of subject A, score of subject B) for query row r
-            t = A::add(diag, __builtin_amdgcn_perm(wb[r >> 1], wa[r >> 1], (r & 1) ? 0x07060302u : 0x05040100u));
+        // The plain recurrence (32-bit kinds only).  Row above the lane's first row: from the neighbouring lane, or from the
+        // stripe border
+        u32 upH, F;
+        if constexpr (MULTI) {
+            upH = prev_lane<LANES, false>(inH, st.Hlast, head);  // lane 0 keeps `old` == the border value
+            F = prev_lane<LANES, false>(inF, st.Fout, head);
         } else {
-            t = A::add(diag, wa[r]);
+            upH = prev_lane<LANES, true>(0u, st.Hlast, head);  // bound_ctrl zero fill == the local-alignment boundary
+            F = prev_lane<LANES, true>(0u, st.Fout, head);
         }
-        diag = st.H[r];
-        const u32 h = A::cell_h(t, st.E[r], F);
-        const u32 hg = A::gap(h, gop);
-        st.E[r] = A::gap_state(A::gap(st.E[r], gex), hg);
-        F = A::gap_state(A::gap(F, gex), hg);
-        st.H[r] = h;
-        // running maximum: folded two rows at a time (a 3-input max where the ISA has one)
-        if (r & 1) maxv = A::fold2(maxv, st.H[r - 1], h);
-        else if (r == R - 1) maxv = A::max2(maxv, h);
+        u32 diag = st.upH_prev;
+        st.upH_prev = upH;
+
+        u32 maxv = st.maxv[0];
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const u32 t = A::add(diag, wa[r]);
+            diag = st.H[r];
+            const u32 h = A::cell_h(t, st.E[r], F);
+            const u32 hg = A::gap(h, gop);
+            st.E[r] = A::gap_state(A::gap(st.E[r], gex), hg);
+            F = A::gap_state(A::gap(F, gex), hg);
+            st.H[r] = h;
+            // running maximum: folded two rows at a time (a 3-input max where the ISA has one)
+            if (r & 1) maxv = A::fold2(maxv, st.H[r - 1], h);
+            else if (r == R - 1) maxv = A::max2(maxv, h);
+        }
+        st.maxv[0] = maxv;
+        st.Hlast = st.H[R - 1];
+        st.Fout = F;
     }
-    st.maxv[0] = maxv;
-    st.Hlast = st.H[R - 1];
-    st.Fout = F;
 }
 
 // Copy one profile tile (global, L2-resident) into LDS.  The tile starts 16 bytes into the LDS
@@ -835,15 +804,24 @@ __device__ __forceinline__ u32 quad_max(u32 v, MAX&& mx) {
     return v;
 }
 
+// maximum of true scores over the 16 lanes of a DPP row, left in all of them
+template <int KIND>
+__device__ __forceinline__ u32 row_max_true(u32 v) {
+    using A = Arith<KIND>;
+    v = A::true_max(v, dpp<0x128, false>(v, v));  // row_ror:8
+    v = A::true_max(v, dpp<0x124, false>(v, v));  // row_ror:4
+    v = A::true_max(v, dpp<0x122, false>(v, v));  // row_ror:2
+    v = A::true_max(v, dpp<0x121, false>(v, v));  // row_ror:1
+    return v;
+}
+
+// group maximum of the plain form (32-bit kinds)
 template <int KIND, int LANES>
 __device__ __forceinline__ u32 group_max(u32 v) {
     using A = Arith<KIND>;
     if constexpr (LANES == 8) return half_row_max(v, [](u32 a, u32 b) { return A::max2(a, b); });
     if constexpr (LANES == 4) return quad_max(v, [](u32 a, u32 b) { return A::max2(a, b); });
-    v = A::max2(v, dpp<0x128, false>(v, v));  // row_ror:8
-    v = A::max2(v, dpp<0x124, false>(v, v));  // row_ror:4
-    v = A::max2(v, dpp<0x122, false>(v, v));  // row_ror:2
-    v = A::max2(v, dpp<0x121, false>(v, v));  // row_ror:1
+    v = row_max_true<KIND>(v);   // (32-bit kinds: their true scores compare like their values)
     if constexpr (LANES == 64) {
         v = A::max2(v, (u32)__shfl_xor((int)v, 16));
         v = A::max2(v, (u32)__shfl_xor((int)v, 32));
@@ -874,9 +852,6 @@ __device__ __forceinline__ u32 group_max(u32 v) {
 // walked the real array, the rest hit junk slots and the zeros array: 16 staging registers, ~3 register copies per step,
 // and write-backs of junk lines.)  The scratch is indexed by the PRODUCER's step ("position"): the last lane emits column
 // c at position c + LANES - 1, so the consumer's block b starts 8 * (LANES - 1) bytes into producer block b.
-#ifndef SWK_BORDER_PEND
-#define SWK_BORDER_PEND 1   // 1: the block after next is loaded one block ahead into 4 registers; 0: loaded where it is needed (exposed latency once per block)
-#endif
 template <int LANES>
 struct Border {
     static constexpr int kBlockCols = 2 * LANES;                 // positions per block: 16 bytes per lane
@@ -898,13 +873,19 @@ struct Border {
 template <int LANES>
 constexpr int border_region_words(int lcap) { return Border<LANES>::blocks(lcap) * Border<LANES>::kBlockWords; }  // per group
 
+// Start handshake (ScanParams::start_signal): this workgroup holds its registers and LDS now — whoever the caller ordered
+// behind the signal cannot take them
+__device__ __forceinline__ void announce_start(const ScanParams& p) {
+    if (p.start_signal && threadIdx.x == 0) {
+        if (atomicAdd(p.work_counter + 1, 1u) + 1u == p.start_quorum)
+            __hip_atomic_fetch_add(p.start_signal, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 // Minimum waves per SIMD the register allocator must leave room for (2nd __launch_bounds__ argument).
 // Packed kinds: 1 (unconstrained) is best — forcing 3-4 waves spills the multi-stripe kernels (-3..4 %).
 // 32-bit kinds: v_add_f32/v_add_u32 co-issue with v_max3_* mostly ACROSS waves (tools/ubench/mix_rate.hip:
 // 99 lanes/clk/CU at 4 waves/SIMD, 80 at 2), so they want occupancy more than registers.
-#ifndef SWK_MIN_WAVES_SCALAR
-#define SWK_MIN_WAVES_SCALAR 0
-#endif
 #ifndef SWK_I32_WAVES3_MAX_R
 #define SWK_I32_WAVES3_MAX_R 32
 #endif
@@ -923,7 +904,6 @@ constexpr int min_waves_of(int KIND, int R, int LANES, bool MULTI) {
     // (168 VGPRs): two waves cover each other's wait states only ~92 % of the time, three reach the issue peak
     if (packed && LANES <= 16 && MULTI && R <= SWK_WAVES3_MAX_R_MULTI) return 3;
     if (packed) return (LANES <= 16 && !MULTI && R <= SWK_WAVES4_MAX_R) ? 4 : (LANES <= 16 && !MULTI && R <= SWK_WAVES3_MAX_R) ? 3 : 2;
-    if (SWK_MIN_WAVES_SCALAR > 0) return SWK_MIN_WAVES_SCALAR;
     // int32 above 32 rows per lane: two waves per SIMD (the registers of the taller stripes; its add/max3 mix cannot
     // co-issue anyway).  Up to 32 rows the third wave is worth more than the spills it causes in the multi-stripe kernels
     // from R = 24 up (two-stripe queries of 850 / 1000 residues: 6.36 / 6.42 with three waves, 6.12 / 6.22 TCUPS with two)
@@ -945,7 +925,9 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
     using BD = Border<LANES>;
     constexpr int SHL1 = Shift<LANES>::kShl1;
     constexpr int kQuadsPerLetterBlock = LANES;  // a lane holds 4 letters: LANES quads per reload
-    constexpr int P = OFFS ? frame_classes(A::kPacked, R, LANES, MULTI, OFFS && A::kPacked) : 1;  // row classes of the column-offset frame
+    static_assert(!A::kPacked || OFFS, "packed kinds run the column-offset recurrence only (sw_launch.hpp: launch_scan_ro)");
+    constexpr bool kUni = A::kPacked;   // the packed kinds' frame (below)
+    constexpr int P = OFFS ? frame_classes(A::kPacked, R, LANES, MULTI, kUni) : 1;  // row classes of the column-offset frame
     __shared__ __attribute__((aligned(16))) unsigned char lds[16 + G::kTileBytes];
     __shared__ __attribute__((aligned(16))) unsigned char rings[MULTI ? BD::ring_bytes(kGroups) : 16];
 
@@ -957,11 +939,7 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
     // (4-lane groups likewise: the four groups of a row in slots 0..3, 4..7, 8..11, 12..15)
     const int slot = LANES < 16 ? (tid & 15) : lane;
     const u32 laneStep = (A::kPacked ? 0x00100010u : 16u) * ((LANES < 16 && head) ? u32(slot + 1) : 1u);
-    if (p.start_signal && tid == 0) {
-        // this workgroup holds its registers and LDS now: whoever the caller ordered behind the signal cannot take them
-        if (atomicAdd(p.work_counter + 1, 1u) + 1u == p.start_quorum)
-            __hip_atomic_fetch_add(p.start_signal, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    announce_start(p);
     // A re-score launch is the tail of its scan: a handful of subjects, each one group's walk, started BEHIND the bulk grid
     // whose older waves win the SIMD's arbitration — measured 0.27 us per step of a wave-wide fp32 group against 0.14 for
     // the same kernel launched ahead of the bulk grid.  Raised priority gives the walk its issue slots.
@@ -995,7 +973,6 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
     //     the border rings need no correction.  The zero levels are the same in every lane of the wave: a window zw of
     //     P + 5 words in scalar registers, zw[k] = a*(u0 + k) with u0 the u of the quad's first step (ScanParams::levels),
     //     and at u = K - 1 every lane lowers all it holds by a*K in the same step, after the quad's last step.
-    constexpr bool kUni = OFFS && A::kPacked;
     const u32 apos = OFFS ? A::pos_word(p.gex_mag) : 0u;
     const u32 apos4 = OFFS ? A::pos_word(4 * p.gex_mag) : 0u;
     const int rq = kUni ? p.renorm_quads : 0;
@@ -1087,12 +1064,14 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
         if constexpr (MULTI) nquads = min(nquads, (p.lcap - 4) >> 2);
         // the same in every lane of the wave (lmax was reduced over its groups): saying so turns the quad loop, its
         // letter-reload test and the frame-lowering segments into scalar control flow (the counter otherwise lives in a
-        // VGPR, with a compare, an exec update and a masked branch per quad).  Single-stripe kernels: +0.5 %; the
-        // multi-stripe kernels schedule worse with it (4 instructions fewer per quad, yet -1 %), so they keep the vector loop
-        if constexpr (!MULTI || SWK_MULTI_SCALAR_LOOP) nquads = __builtin_amdgcn_readfirstlane(nquads);
+        // VGPR, with a compare, an exec update and a masked branch per quad).  Single-stripe kernels: +0.5 %.  The
+        // multi-stripe kernels do the same: rounds 1-3 kept their counters in vector registers (the scalar form measured 1 %
+        // slower then); with the block loop of the LDS border rings it is the faster one (11.39 -> 11.44 TCUPS) and frees
+        // registers
+        nquads = __builtin_amdgcn_readfirstlane(nquads);
         const int len0pad = (len0 + 3) & ~3, len1pad = (len1 + 3) & ~3;
 
-        u32 maxv = OFFS ? 0u : A::kZero;  // OFFS tracks true scores (unbiased), the plain form the kind's own zero
+        u32 maxv = 0u;  // true scores (the plain form, 32-bit kinds only, has no bias either)
         for (int stripe = 0; stripe < p.nstripes; stripe++) {
             const bool first = stripe == 0;
             if constexpr (MULTI) {
@@ -1186,9 +1165,7 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                 if (!first) {
                     const uint4 b0 = *reinterpret_cast<const uint4*>(gIn);
-#if SWK_BORDER_PEND
                     pend = *reinterpret_cast<const uint4*>(gIn + BD::kBlockWords);
-#endif
                     *reinterpret_cast<uint4*>(ringIn + 16 * lane) = b0;
                 } else {
                     *reinterpret_cast<uint4*>(ringIn + 16 * lane) = first_stripe_pairs(2 * lane);
@@ -1216,12 +1193,8 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
                 if (first) {
                     *reinterpret_cast<uint4*>(rIn) = first_stripe_pairs((blk + 1) * BD::kBlockCols + 2 * ln);
                 } else {
-#if SWK_BORDER_PEND
                     *reinterpret_cast<uint4*>(rIn) = pend;
                     pend = *reinterpret_cast<const uint4*>(gb + 2 * (LANES - 1) + (size_t)(blk + 2) * BD::kBlockWords);
-#else
-                    *reinterpret_cast<uint4*>(rIn) = *reinterpret_cast<const uint4*>(gb + 2 * (LANES - 1) + (size_t)(blk + 1) * BD::kBlockWords);
-#endif
                 }
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 nxt = *reinterpret_cast<const uint2*>(inPtr);   // what the last step prefetched was the old block's
@@ -1349,10 +1322,7 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
             } else if constexpr (LANES == 4) {
                 maxv = quad_max(maxv, [](u32 a, u32 b) { return A::true_max(a, b); });
             } else {
-                maxv = A::true_max(maxv, dpp<0x128, false>(maxv, maxv));
-                maxv = A::true_max(maxv, dpp<0x124, false>(maxv, maxv));
-                maxv = A::true_max(maxv, dpp<0x122, false>(maxv, maxv));
-                maxv = A::true_max(maxv, dpp<0x121, false>(maxv, maxv));
+                maxv = row_max_true<KIND>(maxv);
             }
             if constexpr (LANES == 64) {
                 maxv = A::true_max(maxv, (u32)__shfl_xor((int)maxv, 16));
@@ -1374,8 +1344,8 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
             }
         } else {
             maxv = group_max<KIND, LANES>(maxv);
-            sc0 = A::score_lo(maxv);
-            sc1 = A::score_hi(maxv);
+            sc0 = A::score_lo(maxv);   // (32-bit kinds: one subject per group)
+            sc1 = 0;
         }
         if (lane == 0) {
             if (valid0) {

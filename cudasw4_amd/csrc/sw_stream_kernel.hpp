@@ -89,10 +89,7 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
     const int wave = tid >> 6;
     const bool head = lane == 0;
     const u32 laneStep = 0x00100010u;
-    if (p.start_signal && tid == 0) {
-        if (atomicAdd(p.work_counter + 1, 1u) + 1u == p.start_quorum)
-            __hip_atomic_fetch_add(p.start_signal, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    announce_start(p);
     const int n = p.n;
     const int nbatches = (n + kSubjPerBatch - 1) / kSubjPerBatch;
     if ((int)blockIdx.x >= nbatches) return;
@@ -295,9 +292,7 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                 if (!first) {
                     const uint4 b0w = *reinterpret_cast<const uint4*>(gIn);
-#if SWK_BORDER_PEND
                     pend = *reinterpret_cast<const uint4*>(gIn + BD::kBlockWords);
-#endif
                     *reinterpret_cast<uint4*>(ringIn + 16 * lane) = b0w;
                 } else {
                     *reinterpret_cast<uint4*>(ringIn + 16 * lane) = first_stripe_pairs(2 * lane);
@@ -321,12 +316,8 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
                 if (first) {
                     *reinterpret_cast<uint4*>(rIn) = first_stripe_pairs((blk + 1) * BD::kBlockCols + 2 * ln);
                 } else {
-#if SWK_BORDER_PEND
                     *reinterpret_cast<uint4*>(rIn) = pend;
                     pend = *reinterpret_cast<const uint4*>(gb + 2 * (LANES - 1) + (size_t)(blk + 2) * BD::kBlockWords);
-#else
-                    *reinterpret_cast<uint4*>(rIn) = *reinterpret_cast<const uint4*>(gb + 2 * (LANES - 1) + (size_t)(blk + 1) * BD::kBlockWords);
-#endif
                 }
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 nxt = *reinterpret_cast<const uint2*>(inPtr);
@@ -400,11 +391,7 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
             // slot k's maximum over this stripe from the lanes' maxima `lanemax` (true scores), kept in lane k of the group; the
             // scores leave after the round's last stripe (emit_slot below: nothing but this reduction sits between the loops)
             auto finish_slot = [&](int k, u32 lanemax) {
-                u32 mv = lanemax;
-                mv = A::true_max(mv, dpp<0x128, false>(mv, mv));
-                mv = A::true_max(mv, dpp<0x124, false>(mv, mv));
-                mv = A::true_max(mv, dpp<0x122, false>(mv, mv));
-                mv = A::true_max(mv, dpp<0x121, false>(mv, mv));
+                const u32 mv = row_max_true<KIND>(lanemax);
                 if (lane == k) slotAcc = (!MULTI || first) ? mv : A::true_max(slotAcc, mv);
             };
             // ---- the stream, block by block (MULTI: a block transfer behind every kQuadsPerBlock quads)
