@@ -17,3 +17,20 @@ def test_randomised_soak_short(monkeypatch):
     seed = os.environ.get("FUZZ_SEED", "314")
     cases = fuzz_gpu.main(["--seconds", seconds, "--seed", seed, "--driver-bias", "0.3"])
     assert cases >= 20
+
+
+def test_randomised_soak_align_short():
+    """40 cases of `--features align`: hit alignment of letter and PSSM queries through the C ABI (random budgets, CIGAR
+    slots, scratch sizes, expected scores, gap scores up to the documented bound) and, one case in three, the host driver.
+    MI355X: 0.9 s inside the suite, 3.0 s as the first GPU test of a process."""
+    import fuzz_gpu
+    seed = os.environ.get("FUZZ_SEED", "2718")
+    assert fuzz_gpu.main(["--features", "align", "--cases", "40", "--seed", seed]) == 40
+
+
+def test_randomised_soak_pssm_short():
+    """30 cases of `--features pssm`: profile search through both hosts under the hooks, every score and the top 10.
+    MI355X: 2.1 s inside the suite, 3.8 s as the first GPU test of a process."""
+    import fuzz_gpu
+    seed = os.environ.get("FUZZ_SEED", "1618")
+    assert fuzz_gpu.main(["--features", "pssm", "--cases", "30", "--seed", seed]) == 30
