@@ -1696,8 +1696,13 @@ __device__ __forceinline__ void small_merge(unsigned long long (&key)[8], unsign
 #pragma unroll
     for (int e = 0; e < 8; e++) mine = key[e] > mine ? key[e] : mine;
     for (int round = 0; round < k; round++) {
+        // The k-th best is read BEFORE the reduction, not after it: thread 0 inserts m into best[] below, and a wave that
+        // came late to a read placed after the reduction could see an m that landed at k-1, take m <= best[k-1] and leave
+        // the loop alone.  Here the read follows the insertion of the round before (that round's closing barrier) and
+        // precedes this round's (the two barriers inside block_max_u64), so every thread tests the same value.
+        const unsigned long long kth = best[k - 1];
         const unsigned long long m = block_max_u64(mine, wmax);
-        if (m <= best[k - 1]) break;   // uniform: nothing of this chunk can still enter
+        if (m <= kth) break;           // uniform: nothing of this chunk can still enter
         if (mine == m) {               // unique keys: exactly one thread; it drops the element and finds its next best
             mine = 0;
 #pragma unroll

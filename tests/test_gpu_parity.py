@@ -163,7 +163,8 @@ def test_topk_matches_oracle_order():
                                     (150_000, 7, 1 << 20), (131_072, 16_384, 50), (3_000_001, 32, 3), (700, 5, 9), (2049, 1, 100)])
 def test_topk_select_equals_sort_and_oracle(n, k, hi, monkeypatch):
     """sw_topk's radix select (large n) against its full-sort path and the oracle's top-K: heavy ties (few distinct
-    scores: the ties at the threshold are broken by position), all-equal scores, nearly distinct scores, a large k."""
+    scores: the ties at the threshold are broken by position), all-equal scores, nearly distinct scores, a large k.
+    (Adversarial orders, path thresholds, digit borders, negative and fractional scores: tests/test_gpu_topk.py.)"""
     torch, capi, search = gpu_modules()
     rng = np.random.default_rng(n + k)
     scores_i = rng.integers(0, hi, n).astype(np.int32)
