@@ -317,7 +317,8 @@ int32_t border_capacity(int32_t max_len, int lanes) {
 }
 size_t border_bytes_per_wg(int32_t lcap, int lanes) {
     if (lanes == 4) return 0;   // single-stripe kernels only: no border
-    const size_t region = lanes == 16 ? swk::border_region_words<16>(lcap) : lanes == 8 ? swk::border_region_words<8>(lcap) : swk::border_region_words<64>(lcap);
+    // (16-lane groups: the border array and, behind it, the address stream of the packed sw_scan_kernel — 8 + 4 bytes per column)
+    const size_t region = lanes == 16 ? swk::group_region_words<16>(lcap) : lanes == 8 ? swk::group_region_words<8>(lcap) : swk::group_region_words<64>(lcap);
     return (size_t)(swk::kThreads / lanes) * region * sizeof(uint32_t);
 }
 

@@ -393,7 +393,7 @@ struct ScanParams {
     int32_t* ovf_pos;
     int32_t* ovf_count;
     int32_t ovf_check;
-    u32* scratch;              // stripe-border spill: per (workgroup, group) border_region_words(lcap) words
+    u32* scratch;              // stripe-border spill and address stream: per (workgroup, group) group_region_words(lcap) words
     int32_t lcap;
     const u32* zeros;          // >= 64 bytes of the kind's zero pattern (border of the first stripe)
     u32* work_counter;         // zeroed before the launch: next batch to hand out
@@ -587,7 +587,9 @@ struct StripeState {
 // bound_ctrl zero fill — levels that start below zero, and separator columns, which rebuild a lane's state from it.
 // UNI (sw_scan_kernel, packed kinds): the uniform frame — the zero levels depend on the step alone and come from the caller's
 // wave-uniform window zw (scalar registers) instead of st.Zc (sw_scan_kernel explains the frame).
-template <int KIND, int R, int LANES, int BYTE, bool MULTI, bool OFFS = false, int P = 1, bool ZFILL = true, bool UNI = false>
+// ADDR (packed kinds, 16-lane groups): lettersA is the lane's word of the address stream for this step (stream_region_words)
+// and laneStep its slot byte 16 * slot; the two LDS addresses are one byte permute each, nothing travels along the group.
+template <int KIND, int R, int LANES, int BYTE, bool MULTI, bool OFFS = false, int P = 1, bool ZFILL = true, bool UNI = false, bool ADDR = false>
 __device__ __forceinline__ void dp_step(StripeState<KIND, R, P>& st, const unsigned char* tile,
                                         u32 lettersA, u32 lettersB, u32 gop, u32 gex, u32 inH, u32 inF,
                                         u32 apos = 0, bool first = false, u32 wrapP = 0, u32 wrapLast = 0, bool head = false,
@@ -608,7 +610,10 @@ __device__ __forceinline__ void dp_step(StripeState<KIND, R, P>& st, const unsig
     // subject letter(s): shift along the group, lane 0 takes the next letter of its subject
     u32 wa[G::NW];
     u32 wb[G::NW];
-    if constexpr (A::kPacked && LANES <= 16) {
+    static_assert(!ADDR || (A::kPacked && LANES == 16 && OFFS), "the address stream serves the packed kinds on 16-lane groups");
+    if constexpr (ADDR) {
+        // (pa / pb below)
+    } else if constexpr (A::kPacked && LANES <= 16) {
         // both LDS addresses (< 64 KB) travel in one register: one permute, one DPP move and one add for the pair
         constexpr u32 kSel2 = ((u32)(4 + BYTE) << 24) | 0x000c000cu | ((u32)BYTE << 8);  // B's byte -> 31:24, A's -> 15:8
         const u32 inj = __builtin_amdgcn_perm(lettersB, lettersA, kSel2);
@@ -681,8 +686,10 @@ __device__ __forceinline__ void dp_step(StripeState<KIND, R, P>& st, const unsig
         // its first word is used), as many more as it takes where 3-word chunks shift the rows
         constexpr int kChunks0 = G::kWide ? CH::lead_for(kAhead, 4) : 1;
         static_assert(!G::kWide || kChunks0 >= kChunksAll || CH::lead_ok(kChunks0, kAhead, 4), "a score word would be used before its read is issued");
-        const unsigned char* const pa = tile + (st.yA & 0xffffu);
-        const unsigned char* const pb = tile + (st.yA >> 16);
+        // ADDR: byte 1 from the stream word (A: its byte 1, B: its byte 3), byte 0 the lane's slot; the +16 bias of the tile
+        // (load_tile) is an immediate of the reads
+        const unsigned char* const pa = ADDR ? tile + 16 + __builtin_amdgcn_perm(lettersA, laneStep, 0x0c0c0500u) : tile + (st.yA & 0xffffu);
+        const unsigned char* const pb = ADDR ? tile + 16 + __builtin_amdgcn_perm(lettersA, laneStep, 0x0c0c0700u) : tile + (st.yA >> 16);
         u32 tq[G::kWide ? R : 1];
         if constexpr (G::kWide) {
 #pragma unroll
@@ -873,6 +880,20 @@ struct Border {
 template <int LANES>
 constexpr int border_region_words(int lcap) { return Border<LANES>::blocks(lcap) * Border<LANES>::kBlockWords; }  // per group
 
+// Address stream of the packed multi-stripe sw_scan_kernel on 16-lane groups (dp_step<ADDR>).  What a lane needs of the
+// subject letters are the LDS addresses of two profile rows, and those are the same in every stripe of a subject pair: the
+// group writes them ONCE per pair, one word per subject column behind its border array — bits 15:8 hold A's letter *
+// kLetterUnits, bits 31:24 B's, the other two bytes are zero (what lane 0 injected into the systolic address register at
+// every step of every stripe before) — and lane l reads the word of column t - l at step t.  Column 0 is word LANES of
+// the stream; the words of columns -LANES .. -1 and of the columns behind a subject's end hold the padding letter, so a
+// lane that has not reached the subject yet, or has left it, needs no special case.  Columns up to 4 * nquads + LANES - 1
+// <= lcap + LANES - 5 are written: blocks(lcap) * kBlockCols >= lcap + 3 * kBlockCols words hold them.
+template <int LANES>
+constexpr int stream_region_words(int lcap) { return LANES == 16 ? Border<LANES>::blocks(lcap) * Border<LANES>::kBlockCols : 0; }
+// scratch words per group: the border array, then the address stream
+template <int LANES>
+constexpr int group_region_words(int lcap) { return border_region_words<LANES>(lcap) + stream_region_words<LANES>(lcap); }
+
 // Start handshake (ScanParams::start_signal): this workgroup holds its registers and LDS now — whoever the caller ordered
 // behind the signal cannot take them
 __device__ __forceinline__ void announce_start(const ScanParams& p) {
@@ -927,6 +948,7 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
     constexpr int kQuadsPerLetterBlock = LANES;  // a lane holds 4 letters: LANES quads per reload
     static_assert(!A::kPacked || OFFS, "packed kinds run the column-offset recurrence only (sw_launch.hpp: launch_scan_ro)");
     constexpr bool kUni = A::kPacked;   // the packed kinds' frame (below)
+    constexpr bool kAddr = A::kPacked && MULTI && LANES == 16;   // LDS addresses from the pair's address stream (stream_region_words)
     constexpr int P = OFFS ? frame_classes(A::kPacked, R, LANES, MULTI, kUni) : 1;  // row classes of the column-offset frame
     __shared__ __attribute__((aligned(16))) unsigned char lds[16 + G::kTileBytes];
     __shared__ __attribute__((aligned(16))) unsigned char rings[MULTI ? BD::ring_bytes(kGroups) : 16];
@@ -938,7 +960,7 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
     // 8-lane groups: the two groups of a DPP row use the two halves of the row's 16 profile slots (dp_step: laneStep)
     // (4-lane groups likewise: the four groups of a row in slots 0..3, 4..7, 8..11, 12..15)
     const int slot = LANES < 16 ? (tid & 15) : lane;
-    const u32 laneStep = (A::kPacked ? 0x00100010u : 16u) * ((LANES < 16 && head) ? u32(slot + 1) : 1u);
+    const u32 laneStep = kAddr ? 16u * (u32)slot : (A::kPacked ? 0x00100010u : 16u) * ((LANES < 16 && head) ? u32(slot + 1) : 1u);
     announce_start(p);
     // A re-score launch is the tail of its scan: a handful of subjects, each one group's walk, started BEHIND the bulk grid
     // whose older waves win the SIMD's arbitration — measured 0.27 us per step of a wave-wide fp32 group against 0.14 for
@@ -958,7 +980,23 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
     // Stripe border of this group (Border<LANES>): its rings in LDS and its block array in the global scratch
     unsigned char* const ringIn = rings + (MULTI ? group * BD::kGroupBytes : 0);
     unsigned char* const ringOut = ringIn + BD::kInBytes;
-    u32* const gBorder = MULTI ? p.scratch + ((size_t)blockIdx.x * kGroups + group) * (size_t)border_region_words<LANES>(p.lcap) : nullptr;
+    u32* const gBorder = MULTI ? p.scratch + ((size_t)blockIdx.x * kGroups + group) * (size_t)group_region_words<LANES>(p.lcap) : nullptr;
+    // Address stream of this group (stream_region_words), as the loop reads it: the stream of the wave's first group — a
+    // wave-uniform base, which lives and walks in scalar registers — and this lane's byte offset from it at step 0: column
+    // -lane of its own group's stream (the groups of a wave lie < 4 GB apart: a region is a few words per column)
+    // (a global-memory pointer by type: rebuilt from integers it would be a generic one, whose loads count in lgkmcnt too)
+    typedef const __attribute__((address_space(1))) unsigned char* StreamPtr;
+    StreamPtr streamBase = nullptr;
+    u32 streamOff = 0;
+    if constexpr (kAddr) {
+        constexpr int kGroupsPerWave = 64 / LANES;
+        const int g0 = group & ~(kGroupsPerWave - 1);
+        const uintptr_t b = reinterpret_cast<uintptr_t>(p.scratch + ((size_t)blockIdx.x * kGroups + g0) * (size_t)group_region_words<LANES>(p.lcap) +
+                                                        border_region_words<LANES>(p.lcap));
+        streamBase = (StreamPtr)(((uintptr_t)(u32)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
+                                 (uintptr_t)(u32)__builtin_amdgcn_readfirstlane((int)(u32)b));
+        streamOff = 4u * (u32)((group - g0) * group_region_words<LANES>(p.lcap) + LANES - lane);
+    }
 
     // The frame of the column-offset recurrence (dp_step<OFFS>).
     //   * 32-bit kinds: the column frame — a cell of column j is raised by a*(j + LANES), a lane starts every stripe "at
@@ -1070,6 +1108,28 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
         // registers
         nquads = __builtin_amdgcn_readfirstlane(nquads);
         const int len0pad = (len0 + 3) & ~3, len1pad = (len1 + 3) & ~3;
+        // letters j .. j + 3 of a subject (j a multiple of 4: one aligned word; the padding letter behind its end), premultiplied
+        // by kLetterUnits so that a byte << kLetterShift is the byte offset of the letter's profile row
+        auto letters4 = [&](const int8_t* s, int lenpad, int j) -> u32 {
+            u32 w = 0x14141414u;
+            if (j < lenpad) w = *reinterpret_cast<const u32*>(s + j);
+            return w * (u32)G::kLetterUnits;
+        };
+        if constexpr (kAddr) {
+            // The pair's address stream (stream_region_words), once for all stripes: lane l writes the four words of columns
+            // 4c .. 4c + 3 for c = l, l + LANES, ... up to column 4 * nquads + LANES - 1, and the padding word of column
+            // l - LANES.  Each subject pads from its own end; a group without a subject B has len1 = 0.
+            u32* const sw = gBorder + border_region_words<LANES>(p.lcap) + LANES;   // the word of column 0
+            sw[lane - LANES] = (u32)(kPadLetter * G::kLetterUnits) * 0x01000100u;
+            for (int c = lane; c < nquads + LANES / 4; c += LANES) {
+                const u32 a = letters4(s0, len0pad, 4 * c), b = letters4(s1, len1pad, 4 * c);
+                // B's byte k -> bits 31:24, A's -> bits 15:8
+                *reinterpret_cast<uint4*>(sw + 4 * c) = make_uint4(__builtin_amdgcn_perm(b, a, 0x040c000cu), __builtin_amdgcn_perm(b, a, 0x050c010cu),
+                                                                   __builtin_amdgcn_perm(b, a, 0x060c020cu), __builtin_amdgcn_perm(b, a, 0x070c030cu));
+            }
+            // the group's own lanes read it, from the first stripe's acquire fence on (the border arrays travel the same way)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        }
 
         u32 maxv = 0u;  // true scores (the plain form, 32-bit kinds only, has no bias either)
         for (int stripe = 0; stripe < p.nstripes; stripe++) {
@@ -1124,14 +1184,17 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
             // subject letters: lane l holds letters 4*LANES*blk + 4l .. +3 of each subject, premultiplied
             // by kLetterUnits so that a byte << kLetterShift is the byte offset of the letter's profile row
             auto fetch = [&](const int8_t* s, int lenpad, int blk) -> u32 {
-                const int j = blk * (4 * LANES) + lane * 4;
-                u32 w = 0x14141414u;
-                if (j < lenpad) w = *reinterpret_cast<const u32*>(s + j);
-                return w * (u32)G::kLetterUnits;
+                if constexpr (kAddr) return 0u;   // (the address stream has them)
+                else return letters4(s, lenpad, blk * (4 * LANES) + lane * 4);
             };
             u32 nextA = fetch(s0, len0pad, 0);
             u32 nextB = A::kPacked ? fetch(s1, len1pad, 0) : 0u;
             u32 lettersA = 0, lettersB = 0;
+            // kAddr: the stream as this stripe walks it — the scalar base moves on by four words per quad, the steps of a quad
+            // are immediate offsets — and the word of the step to come, requested one step ahead like the border pair (nxt)
+            StreamPtr streamAt = streamBase;
+            auto stream_word = [&](int k) -> u32 { return ((const __attribute__((address_space(1))) u32*)(streamAt + (size_t)streamOff))[k]; };
+            u32 nxtW = 0;
 
             // Stripe border (MULTI only; Border<LANES>).  Lane 0 walks the IN ring, the last lane the OUT ring; the other
             // lanes read the ring's first pair over and over and write into their dummy slots.
@@ -1172,6 +1235,7 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 nxt = *reinterpret_cast<const uint2*>(inPtr);
+                if constexpr (kAddr) nxtW = stream_word(0);
             }
             // end of block `blk` (all of its steps are done): the OUT ring's first block goes to the scratch, the IN ring
             // takes the next block, the load of the one after that is issued
@@ -1182,7 +1246,7 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
                 asm volatile("" : "+v"(t));
                 const int ln = t & (LANES - 1), grp = t / LANES;
                 unsigned char* const rIn = rings + grp * BD::kGroupBytes + 16 * ln;
-                u32* const gb = p.scratch + ((size_t)blockIdx.x * kGroups + grp) * (size_t)border_region_words<LANES>(p.lcap) + 4 * ln;
+                u32* const gb = p.scratch + ((size_t)blockIdx.x * kGroups + grp) * (size_t)group_region_words<LANES>(p.lcap) + 4 * ln;
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 if (!last) {
                     const uint4 v = *reinterpret_cast<const uint4*>(rIn + BD::kInBytes);
@@ -1220,7 +1284,7 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
                 }
             };
             auto quad = [&](int q) {
-                if ((q & (kQuadsPerLetterBlock - 1)) == 0) {
+                if (!kAddr && (q & (kQuadsPerLetterBlock - 1)) == 0) {
                     lettersA = nextA; lettersB = nextB;
                     nextA = fetch(s0, len0pad, q / kQuadsPerLetterBlock + 1);
                     if constexpr (A::kPacked) nextB = fetch(s1, len1pad, q / kQuadsPerLetterBlock + 1);
@@ -1240,8 +1304,17 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
                             nxt = *reinterpret_cast<const uint2*>(inPtr + 8 * (BYTE + 1));
                         }
                     }
-                    dp_step<KIND, R, LANES, BYTE, MULTI, OFFS, P, true, kUni>(st, lds, lettersA, lettersB, p.gop, p.gex, in.x, in.y, apos, first,
-                                                                          p.wrap_class, p.wrap_last, head, laneStep, zw);
+                    if constexpr (kAddr) {
+                        lettersA = nxtW;
+                        if constexpr (BYTE == 3) {
+                            streamAt += 16;
+                            nxtW = stream_word(0);
+                        } else {
+                            nxtW = stream_word(BYTE + 1);
+                        }
+                    }
+                    dp_step<KIND, R, LANES, BYTE, MULTI, OFFS, P, true, kUni, kAddr>(st, lds, lettersA, lettersB, p.gop, p.gex, in.x, in.y, apos, first,
+                                                                                 p.wrap_class, p.wrap_last, head, laneStep, zw);
                     if constexpr (kUni && BYTE == 3) {
                         if (lower) lower_frame();
                     }
@@ -1252,8 +1325,10 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
                 border_step(std::integral_constant<int, 2>{});
                 border_step(std::integral_constant<int, 3>{});
                 if constexpr (MULTI) outPtr += walkOut;
-                lettersA = dpp<SHL1, true>(0u, lettersA);
-                if constexpr (A::kPacked) lettersB = dpp<SHL1, true>(0u, lettersB);
+                if constexpr (!kAddr) {
+                    lettersA = dpp<SHL1, true>(0u, lettersA);
+                    if constexpr (A::kPacked) lettersB = dpp<SHL1, true>(0u, lettersB);
+                }
                 if constexpr (OFFS && A::kWindow) {  // the windows move on by four columns (kUni: steps; its levels are scalar)
                     if constexpr (!kUni) {
 #pragma unroll

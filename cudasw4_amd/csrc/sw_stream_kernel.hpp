@@ -97,7 +97,7 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
 
     unsigned char* const ringIn = rings + (MULTI ? group * BD::kGroupBytes : 0);
     unsigned char* const ringOut = ringIn + BD::kInBytes;
-    u32* const gBorder = MULTI ? p.scratch + ((size_t)blockIdx.x * kGroups + group) * (size_t)border_region_words<LANES>(p.lcap) : nullptr;
+    u32* const gBorder = MULTI ? p.scratch + ((size_t)blockIdx.x * kGroups + group) * (size_t)group_region_words<LANES>(p.lcap) : nullptr;
 
     const int a = p.gex_mag;
     const u32 apos = A::pos_word(a);
@@ -305,7 +305,7 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
                 asm volatile("" : "+v"(t));
                 const int ln = t & (LANES - 1), grp = t / LANES;
                 unsigned char* const rIn = rings + grp * BD::kGroupBytes + 16 * ln;
-                u32* const gb = p.scratch + ((size_t)blockIdx.x * kGroups + grp) * (size_t)border_region_words<LANES>(p.lcap) + 4 * ln;
+                u32* const gb = p.scratch + ((size_t)blockIdx.x * kGroups + grp) * (size_t)group_region_words<LANES>(p.lcap) + 4 * ln;
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 if (!last) {
                     const uint4 v = *reinterpret_cast<const uint4*>(rIn + BD::kInBytes);
