@@ -34,7 +34,7 @@ EXPORTS = ["sw_batch_create", "sw_batch_destroy", "sw_scan_batch", "sw_batch_joi
            "sw_set_rows_pipeline_slot", "sw_packed_launch_falls_back", "sw_scan_partition_counted", "sw_rescore_overflow_pipelined", "sw_rescore_overflow_pipelined_temp_bytes", "sw_measure_valu_rate",
            "sw_align_hits"]
 # ... and include/cudasw4_amd_pssm.h (profile search: a position-specific scoring matrix as the query)
-PSSM_EXPORTS = ["sw_set_query_pssm", "sw_query_is_pssm", "sw_align_hits_pssm"]
+PSSM_EXPORTS = ["sw_set_query_pssm", "sw_query_is_pssm", "sw_align_hits_pssm", "sw_pssm_accumulate"]
 
 
 # sw_align_hits (include/cudasw4_amd.h): result records, statuses, flags, CIGAR op codes
@@ -304,6 +304,32 @@ def align_hits_pssm(ctx, pssm, consensus, qlen, n, chars, offsets, lengths, max_
                    ctypes.cast(ev, ctypes.c_void_p) if ev is not None else None, stream)
     check(f(ctx.handle if ctx is not None else None, ctypes.byref(a), pssm or None))
     return int(need.value)
+
+
+class _PssmAccumulateArgs(ctypes.Structure):
+    _fields_ = [("query", ctypes.c_void_p), ("qlen", ctypes.c_int32), ("n", ctypes.c_int32), ("chars", ctypes.c_void_p),
+                ("offsets", ctypes.c_void_p), ("lengths", ctypes.c_void_p), ("results", ctypes.c_void_p),
+                ("cigar", ctypes.c_void_p), ("include", ctypes.c_void_p), ("counts", ctypes.c_void_p),
+                ("weights", ctypes.c_void_p), ("wcounts", ctypes.c_void_p), ("used", ctypes.c_void_p),
+                ("phase_events", ctypes.c_void_p), ("stream", ctypes.c_void_p)]
+
+
+def pssm_accumulate(ctx, query, qlen, n, chars, offsets, lengths, results, cigar, include, counts, weights, wcounts, used,
+                    stream=0, phase_events=None):
+    """sw_pssm_accumulate (include/cudasw4_amd_pssm.h): residue counts (uint32, qlen x 20), sequence weights (uint64, n + 1,
+    the master last) and weighted counts (uint64, qlen x 20) of the n hits sw_align_hits / sw_align_hits_pssm aligned, plus
+    the master `query`.  Every buffer is a device pointer as an integer; query and include may be 0.  Asynchronous on
+    `stream`.  phase_events: 3 hipEvent_t handles (before, between and after the two launches) or None."""
+    if not hasattr(lib, "sw_pssm_accumulate"):
+        raise SwError(-1, "this build of libcudasw4_amd.so has no sw_pssm_accumulate")
+    f = lib.sw_pssm_accumulate
+    if f.argtypes is None:   # bound on first use (CUDASW4_AMD_LIB may name an older build)
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(_PssmAccumulateArgs)]
+    ev = (ctypes.c_void_p * 3)(*phase_events) if phase_events is not None else None
+    a = _PssmAccumulateArgs(query or None, qlen, n, chars or None, offsets or None, lengths or None, results or None,
+                            cigar or None, include or None, counts or None, weights or None, wcounts or None, used or None,
+                            ctypes.cast(ev, ctypes.c_void_p) if ev is not None else None, stream or None)
+    check(f(ctx.handle if ctx is not None else None, ctypes.byref(a)))
 
 
 def topk_temp_bytes(n, k):

@@ -3,6 +3,8 @@
 // SURVEY.md Appendix D); the work is done by SearchDriver through libcudasw4_amd.so.
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
+#include <cctype>
 #include <chrono>
 #include <cstdlib>
 #include <deque>
@@ -17,6 +19,7 @@
 #include "cli_options.hpp"
 #include "db_format.hpp"
 #include "hit_alignment.hpp"
+#include "pssm_build.hpp"
 #include "pssm_query.hpp"
 #include "search_driver.hpp"
 #include "sequence_reader.hpp"
@@ -88,6 +91,53 @@ void reportScan(const ProgramOptions& o, const ScanResult& r) {
     else std::cout << "Done.\n";
 }
 
+// --iterations / --outPssm: the rounds of one query behind its first scan (pssm_build.hpp; DESIGN.md "Building a PSSM").
+struct IterationResult {
+    std::vector<int8_t> built;              // the PSSM built from the last round's results
+    std::vector<HitAlignment> alignments;   // the last round's results aligned against that round's scoring
+};
+
+// master: the query's letters (a PSSM input: the residue column of its file); first: the PSSM of round 1, or nullptr (the
+// letters).  r: in, the results of round 1; out, those of the last round.  Every round builds a PSSM from its results; round
+// k + 1 scans with the one of round k.  Stops after --iterations rounds, or when a round includes the ids the round before
+// included.
+IterationResult runIterations(const ProgramOptions& o, SearchDriver& driver, PssmBuilder& builder, int64_t queryNum, const std::string& master,
+                              const int8_t* first, ScanResult& r) {
+    const int32_t qlen = int32_t(master.size());
+    std::vector<int8_t> scoring;
+    if (first) scoring.assign(first, first + size_t(qlen) * kPssmColumns);
+    std::vector<int64_t> previous;
+    IterationResult out;
+    for (int round = 1;; round++) {
+        PssmBuildInfo info;
+        out.built = builder.build(master.data(), qlen, scoring.empty() ? nullptr : scoring.data(), r.referenceIds.data(),
+                                  r.scores.data(), r.scores.size(), o.inclusionScore, o.pseudocount, &info);
+        out.alignments = std::move(info.alignments);
+        std::vector<int64_t> included;
+        for (size_t i = 0; i < info.included.size(); i++)
+            if (info.included[i]) included.push_back(r.referenceIds[i]);
+        std::sort(included.begin(), included.end());
+        const bool converged = round > 1 && included == previous;
+        if (o.verbose)
+            std::cout << "Query " << queryNum << " round " << round << ": " << r.scores.size() << " results, " << info.used
+                      << " in the PSSM, " << info.belowScore << " below the inclusion score, " << info.noTrace << " without a trace, "
+                      << info.copies << " copies of the query, lambda " << info.lambda
+                      << (converged && round < o.iterations ? ", converged" : "") << "\n";
+        if (round >= o.iterations || converged) break;
+        previous = std::move(included);
+        scoring = out.built;
+        submit_pssm(driver, scoring.data(), qlen);
+        r = driver.collect();
+    }
+    if (!o.outPssm.empty()) {
+        std::string consensus = master;
+        for (char& c : consensus)
+            if (!(std::isalpha((unsigned char)c) || c == '*' || c == '-')) c = 'X';
+        write_ascii_pssm(o.outPssm + "." + std::to_string(queryNum) + ".pssm", out.built.data(), qlen, consensus);
+    }
+    return out;
+}
+
 // All queries of a file (main.cu:217-260), one at a time like the reference — unless the DB's shards are small enough for
 // the tail hand-over (SearchDriver::prefersTwoInFlight: resident shards of a few rounds of workgroups, or a query that is
 // scanned in a few milliseconds; the next query's launch fills the slots the current one's last round leaves idle: +4 %
@@ -98,7 +148,7 @@ void reportScan(const ProgramOptions& o, const ScanResult& r) {
 // query's line is printed when its results are in.
 // aligner: non-null with --alignments / --pssmAlignments (every query's hits are aligned right after its collect, against that query)
 void processQueryFile(const std::string& file, const ProgramOptions& o, SearchDriver& driver, std::ostream& out, bool interactive,
-                      HitAligner* aligner) {
+                      HitAligner* aligner, PssmBuilder* iteration = nullptr) {
     SequenceReader reader(file);
     struct Pending { int64_t num; std::string header, sequence; };
     std::deque<Pending> pending;
@@ -106,6 +156,7 @@ void processQueryFile(const std::string& file, const ProgramOptions& o, SearchDr
     const char* pipe = std::getenv("CUDASW4_AMD_PIPELINE");
     // how many queries may be pending once a query of this length has been submitted
     auto max_in_flight = [&](size_t queryLength) {
+        if (iteration) return 1;   // the rounds of a query are scans of their own: nothing else may be in flight
         if (pipe) return pipe[0] == '1' ? 2 : 1;
         return driver.preferredInFlight(int32_t(std::min<size_t>(queryLength, size_t(INT32_MAX))));
     };
@@ -117,9 +168,12 @@ void processQueryFile(const std::string& file, const ProgramOptions& o, SearchDr
         std::cout.flush();
         ScanResult r = driver.collect();
         reportScan(o, r);
+        IterationResult rounds;
+        if (iteration) rounds = runIterations(o, driver, *iteration, q.num, q.sequence, nullptr, r);
         if (o.numTopOutputs > 0 || interactive) {
             std::vector<HitAlignment> alignments;
-            if (aligner) alignments = aligner->align(q.sequence.data(), int32_t(q.sequence.size()), r);
+            if (aligner && iteration) alignments = std::move(rounds.alignments);
+            else if (aligner) alignments = aligner->align(q.sequence.data(), int32_t(q.sequence.size()), r);
             const std::vector<HitAlignment>* al = aligner ? &alignments : nullptr;
             if (o.outputMode == ProgramOptions::OutputMode::Plain) {
                 (interactive ? std::cout : out) << "Query " << q.num << ", header" << q.header << ", length " << q.sequence.size()
@@ -153,16 +207,20 @@ void processQueryFile(const std::string& file, const ProgramOptions& o, SearchDr
 
 // One --pssm file: a single query (number 0 of its "file"), printed like a query of a query file; header = the file's base name
 // aligner: non-null with --pssmAlignments (the hits are aligned against the PSSM; '=' / 'X' against the file's residue column)
-void processPssmQuery(const PssmQuery& q, const ProgramOptions& o, SearchDriver& driver, std::ostream& out, HitAligner* aligner) {
+void processPssmQuery(const PssmQuery& q, const ProgramOptions& o, SearchDriver& driver, std::ostream& out, HitAligner* aligner,
+                      PssmBuilder* iteration = nullptr) {
     driver.totalTimerStart();
     std::cout << "Processing query " << 0 << " ... ";
     std::cout.flush();
     submit_pssm(driver, q.scores.data(), q.length());
     ScanResult r = driver.collect();
     reportScan(o, r);
+    IterationResult rounds;
+    if (iteration) rounds = runIterations(o, driver, *iteration, 0, q.consensus, q.scores.data(), r);
     if (o.numTopOutputs > 0) {
         std::vector<HitAlignment> alignments;
-        if (aligner) alignments = aligner->align(q.scores.data(), q.length(), q.consensus.data(), r);
+        if (aligner && iteration) alignments = std::move(rounds.alignments);
+        else if (aligner) alignments = aligner->align(q.scores.data(), q.length(), q.consensus.data(), r);
         const std::vector<HitAlignment>* al = aligner ? &alignments : nullptr;
         if (o.outputMode == ProgramOptions::OutputMode::Plain) {
             out << "Query " << 0 << ", header " << q.name << ", length " << q.length() << ", num overflows " << r.stats.numOverflows << "\n";
@@ -192,6 +250,13 @@ int main(int argc, char** argv) {
             throw std::runtime_error("--pssm cannot be combined with --alignments: use --pssmAlignments to align the results of every query, PSSM queries included");
         if (!options.pssmFiles.empty() && options.interactive)
             throw std::runtime_error("--pssm cannot be combined with --interactive");
+        if (options.iterations < 1) throw std::runtime_error("--iterations must be at least 1");
+        if (options.buildsPssm() && !options.haveInclusionScore)
+            throw std::runtime_error("--iterations above 1 and --outPssm need --inclusionScore S: results go into the PSSM by raw score "
+                                     "(at least S), because this program has no E-values");
+        if (!(options.pseudocount > 0)) throw std::runtime_error("--pseudocount must be positive");
+        if (options.buildsPssm() && options.interactive) throw std::runtime_error("--iterations / --outPssm cannot be combined with --interactive");
+        if (options.buildsPssm() && options.numTopOutputs < 1) throw std::runtime_error("--iterations / --outPssm need --top of at least 1: the PSSM is built from the reported results");
         std::vector<PssmQuery> pssmQueries;
         for (const auto& file : options.pssmFiles) pssmQueries.push_back(read_ascii_pssm(file));
         std::vector<int> deviceIds;
@@ -239,14 +304,17 @@ int main(int argc, char** argv) {
         }
         if (options.loadFullDBToGpu) driver.prefetchDBToGpus();
         std::unique_ptr<HitAligner> aligner;
-        if (options.reportAlignments()) aligner = std::make_unique<HitAligner>(driver);
+        if (options.reportAlignments() || options.buildsPssm()) aligner = std::make_unique<HitAligner>(driver);
+        std::unique_ptr<PssmBuilder> iteration;   // (non-null: every query goes through its rounds)
+        if (options.buildsPssm()) iteration = std::make_unique<PssmBuilder>(driver, *aligner);
+        HitAligner* const reporting = options.reportAlignments() ? aligner.get() : nullptr;   // (alignments are printed)
 
         if (!options.interactive) {
             size_t nextPssm = 0;
             for (const auto& input : options.inputs) {
                 std::cout << "Processing query file " << input.path << "\n";
-                if (input.pssm) processPssmQuery(pssmQueries[nextPssm++], options, driver, outputfile, aligner.get());
-                else processQueryFile(input.path, options, driver, outputfile, false, aligner.get());
+                if (input.pssm) processPssmQuery(pssmQueries[nextPssm++], options, driver, outputfile, reporting, iteration.get());
+                else processQueryFile(input.path, options, driver, outputfile, false, reporting, iteration.get());
             }
         } else {
             // main.cu:336-424

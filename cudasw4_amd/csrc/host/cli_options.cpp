@@ -34,6 +34,10 @@ void printOptions(const ProgramOptions& o) {
     for (size_t i = 0; i < o.queryFiles.size(); i++) std::cout << "queryFile " << i << " : " << o.queryFiles[i] << "\n";
     for (size_t i = 0; i < o.pssmFiles.size(); i++) std::cout << "pssmFile " << i << " : " << o.pssmFiles[i] << "\n";
     if (o.pssmAlignments) std::cout << "pssmAlignments: " << o.pssmAlignments << "\n";
+    if (o.iterations != 1) std::cout << "iterations: " << o.iterations << "\n";
+    if (o.haveInclusionScore) std::cout << "inclusionScore: " << o.inclusionScore << "\n";
+    if (o.pseudocount != 10.0) std::cout << "pseudocount: " << o.pseudocount << "\n";
+    if (!o.outPssm.empty()) std::cout << "outPssm: " << o.outPssm << "\n";
     std::cout << "blosum: " << substitution_matrix(o.matrix).name << "\n";
     std::cout << "singlePassType: " << to_string(o.kernels.singlePassType) << "\n";
     std::cout << "manyPassType_small: " << to_string(o.kernels.manyPassType_small) << "\n";
@@ -72,6 +76,10 @@ bool parseArgs(int argc, char** argv, ProgramOptions& o) {
         else if (arg == "--interactive") o.interactive = true;
         else if (arg == "--alignments") o.alignments = true;
         else if (arg == "--pssmAlignments") o.pssmAlignments = true;
+        else if (arg == "--iterations") o.iterations = std::atoi(value(i).c_str());
+        else if (arg == "--inclusionScore") { o.inclusionScore = std::atoi(value(i).c_str()); o.haveInclusionScore = true; }
+        else if (arg == "--pseudocount") o.pseudocount = std::atof(value(i).c_str());
+        else if (arg == "--outPssm") o.outPssm = value(i);
         else if (arg == "--printLengthPartitions") o.printLengthPartitions = true;
         else if (arg == "--prefetchDBFile") o.prefetchDBFile = true;
         else if (arg == "--top") o.numTopOutputs = std::atoi(value(i).c_str());
@@ -137,6 +145,13 @@ void printHelp(char** argv) {
     std::cout << "      --gex val : Gap extend score. Overwrites our blosum-dependent default score.\n";
     std::cout << "      --mat val: Set substitution matrix. Supported values: blosum45, blosum50, blosum62, blosum80. Default: blosum62\n"
                  "        (with suffix _25: the full 25-letter table for the query letters B, J, Z, X, *)\n\n";
+    std::cout << "   Iterated profile search\n";
+    std::cout << "      --iterations N : N rounds per query (N >= 1, default 1). Round r + 1 scans with the PSSM built from the results of round r\n"
+                 "        (the --top list); the results printed are the last round's. Stops early when the set of included results repeats.\n";
+    std::cout << "      --inclusionScore S : Results with a raw score of at least S go into the PSSM (there are no E-values). Mandatory with\n"
+                 "        --iterations above 1 and with --outPssm.\n";
+    std::cout << "      --pseudocount B : Weight of the substitution-matrix pseudo-frequencies, B > 0. Default val = " << d.pseudocount << "\n";
+    std::cout << "      --outPssm PREFIX : Write the PSSM built from the last round's results to PREFIX.<query number>.pssm (NCBI ASCII, as --pssm reads)\n\n";
     std::cout << "   Memory\n";
     std::cout << "      --maxGpuMem val : Try not to use more than val bytes of gpu memory per gpu. Uses all available gpu memory by default\n";
     std::cout << "      --maxTempBytes val : Size of temp storage in GPU memory. Can use suffix K,M,G. Default val = " << d.memory.maxTempBytes << "\n";

@@ -25,6 +25,15 @@ struct ProgramOptions {
     // of a PSSM against the residue column of its file)
     bool pssmAlignments = false;
     bool reportAlignments() const { return alignments || pssmAlignments; }
+    // Iterated profile search (pssm_build.hpp; an extension): --iterations N rounds, each scanning with the PSSM built from
+    // the round before's reported hits of raw score >= --inclusionScore (there are no E-values); --pseudocount is the
+    // conversion's beta; --outPssm PREFIX writes PREFIX.<query number>.pssm
+    int iterations = 1;
+    bool haveInclusionScore = false;
+    int inclusionScore = 0;
+    double pseudocount = 10.0;
+    std::string outPssm;
+    bool buildsPssm() const { return iterations > 1 || !outPssm.empty(); }
     bool prefetchDBFile = false;
     int numTopOutputs = 10;
     int gop = -11;

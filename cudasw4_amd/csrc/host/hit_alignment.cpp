@@ -90,6 +90,7 @@ std::vector<HitAlignment> HitAligner::align(const char* query, int32_t qlen, con
 
 std::vector<HitAlignment> HitAligner::align(const char* query, int32_t qlen, const int64_t* ids, const int32_t* scores,
                                             size_t n) {
+    residentHits_ = 0;
     if (n == 0) return std::vector<HitAlignment>();
     if (qlen <= 0 || !query || !ids || !scores) throw std::runtime_error("hit alignment: empty query or null hit list");
     // the query encoded as the scan encoded it
@@ -105,6 +106,7 @@ std::vector<HitAlignment> HitAligner::align(const int8_t* pssm, int32_t qlen, co
 
 std::vector<HitAlignment> HitAligner::align(const int8_t* pssm, int32_t qlen, const char* consensus, const int64_t* ids,
                                             const int32_t* scores, size_t n) {
+    residentHits_ = 0;
     if (n == 0) return std::vector<HitAlignment>();
     if (qlen <= 0 || !pssm || !ids || !scores) throw std::runtime_error("hit alignment: empty PSSM or null hit list");
     for (int32_t i = 0; i < qlen; i++)
@@ -189,7 +191,24 @@ std::vector<HitAlignment> HitAligner::run(const int8_t* codes, const int8_t* pss
         const uint32_t* w = cigar.data() + res[i].cigar_offset;
         out[i].cigar.assign(w, w + res[i].cigar_len);
     }
+    residentHits_ = n;
     return out;
+}
+
+HitAligner::Resident HitAligner::resident() const {
+    Resident r;
+    r.device = device_;
+    r.ctx = ctx_;
+    r.stream = stream_;
+    r.n = residentHits_;
+    if (r.n) {
+        r.chars = static_cast<const int8_t*>(buf_[kChars]);
+        r.offsets = static_cast<const uint64_t*>(buf_[kOffsets]);
+        r.lengths = static_cast<const int32_t*>(buf_[kLengths]);
+        r.results = static_cast<const sw_align_result*>(buf_[kResults]);
+        r.cigar = static_cast<const uint32_t*>(buf_[kCigar]);
+    }
+    return r;
 }
 
 }  // namespace swh

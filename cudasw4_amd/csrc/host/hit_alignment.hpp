@@ -43,6 +43,22 @@ public:
                                     const int32_t* scores, size_t n);
     std::vector<HitAlignment> align(const int8_t* pssm, int32_t qlen, const char* consensus, const ScanResult& r);
 
+    // What the last align() left on the device: the hits' subjects, results and CIGAR words in the layout sw_align_hits
+    // was given them, for a consumer that goes on with them there (pssm_build.hpp).  All work of the aligner is complete
+    // when align() returns; the pointers are valid until the next align().  n == 0: there was no such call, or no hit.
+    struct Resident {
+        int device = 0;
+        sw_ctx* ctx = nullptr;
+        hipStream_t stream = nullptr;
+        const int8_t* chars = nullptr;
+        const uint64_t* offsets = nullptr;
+        const int32_t* lengths = nullptr;
+        const sw_align_result* results = nullptr;
+        const uint32_t* cigar = nullptr;
+        size_t n = 0;
+    };
+    Resident resident() const;
+
 private:
     // both forms behind the encoding of the query.  pssm == nullptr: `codes` are the query's codes; else `codes` are the
     // consensus codes (nullptr: none)
@@ -56,6 +72,7 @@ private:
     enum { kQuery, kPssm, kChars, kOffsets, kLengths, kScores, kResults, kCigar, kCigarOffsets, kTemp, kBuffers };
     void* buf_[kBuffers] = {};
     size_t cap_[kBuffers] = {};
+    size_t residentHits_ = 0;
 };
 
 }  // namespace swh

@@ -7,6 +7,7 @@
 #include "pssm_query.hpp"
 
 #include <cctype>
+#include <cstdio>
 #include <cstdlib>
 #include <fstream>
 #include <sstream>
@@ -98,6 +99,34 @@ PssmQuery read_ascii_pssm(const std::string& path) {
     return q;
 }
 
+void write_ascii_pssm(const std::string& path, const int8_t* pssm, int32_t length, const std::string& consensus) {
+    if (!pssm || length <= 0) throw std::runtime_error("empty PSSM");
+    if (consensus.size() != size_t(length))
+        throw std::runtime_error("consensus has " + std::to_string(consensus.size()) + " residues, the PSSM " + std::to_string(length) + " rows");
+    std::ofstream out(path);
+    if (!out) throw std::runtime_error("Cannot open file " + path);
+    char buf[32];
+    out << "\nLast position-specific scoring matrix computed, weighted observed percentages rounded down, "
+           "information per position, and relative weight of gapless real matches to pseudocounts\n";
+    out << "           ";
+    for (int c = 0; c < 20; c++) {
+        std::snprintf(buf, sizeof buf, "%5c", kColumnLetters[c]);
+        out << buf;
+    }
+    out << "\n";
+    for (int32_t i = 0; i < length; i++) {
+        std::snprintf(buf, sizeof buf, "%5d %c  ", int(i + 1), consensus[size_t(i)]);
+        out << buf;
+        for (int c = 0; c < 20; c++) {
+            std::snprintf(buf, sizeof buf, "%5d", int(pssm[size_t(i) * kPssmColumns + c]));
+            out << buf;
+        }
+        out << "\n";
+    }
+    out.flush();
+    if (!out) throw std::runtime_error("Cannot write file " + path);
+}
+
 void submit_pssm(SearchDriver& driver, const int8_t* pssm, int32_t length) {
     if (!pssm || length <= 0) throw std::runtime_error("empty PSSM");
     if (length > SW_PSSM_MAX_QUERY_LEN) throw std::runtime_error("PSSM too long");
@@ -110,6 +139,17 @@ void submit_pssm(SearchDriver& driver, const int8_t* pssm, int32_t length) {
 }  // namespace swh
 
 #ifdef SWH_DRIVER_CAPI   // libcudasw4_host.so (with driver_capi.cpp); `align` links the functions above alone
+extern "C" int swdrv_write_pssm_ascii(const char* path, const int8_t* pssm, int32_t qlen, const char* consensus) {
+    try {
+        if (!path || !consensus) throw std::runtime_error("null path or consensus");
+        swh::write_ascii_pssm(path, pssm, qlen, consensus);
+        return 0;
+    } catch (const std::exception& e) {
+        swh::set_driver_error(e.what());
+        return -1;
+    }
+}
+
 extern "C" int swdrv_scan_submit_pssm(swdrv* d, const int8_t* pssm, int32_t qlen) {
     try {
         if (!d || !d->driver) throw std::runtime_error("null driver");

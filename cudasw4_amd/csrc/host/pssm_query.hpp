@@ -27,6 +27,11 @@ struct PssmQuery {
 // int8 or non-consecutive indices.  No GPU involved.
 PssmQuery read_ascii_pssm(const std::string& path);
 
+// The writer of that format (align --outPssm): the 20 standard columns of `pssm` (length x kPssmColumns; column 20 is not
+// part of the format) under the header, one line per position with its consensus residue; the layout of the Python
+// module's pssm.write_ascii, which read_ascii_pssm and pssm.read_ascii read back.  No GPU involved.
+void write_ascii_pssm(const std::string& path, const int8_t* pssm, int32_t length, const std::string& consensus);
+
 // SearchDriver::submit for a PSSM (pssm: length x kPssmColumns int8, column 20 negative in every row; copied):
 // collect() returns its results like a letter query's, and a letter query may be in flight beside it.
 void submit_pssm(SearchDriver& driver, const int8_t* pssm, int32_t length);

@@ -24,7 +24,7 @@ EXPORTS = ["swdrv_last_error", "swdrv_create", "swdrv_destroy", "swdrv_open_db",
            "swdrv_bind_to_numa_node", "swdrv_device_numa_node", "swdrv_window_stats", "swdrv_service_launches",
            "swdrv_tail_overlaps", "swdrv_prefers_two_in_flight", "swdrv_pipeline_launches", "swdrv_handshake_active", "swdrv_preferred_in_flight",
            "swdrv_latency_scans", "swdrv_plan_runs_mode", "swdrv_align_hits", "swdrv_scan_pssm", "swdrv_scan_submit_pssm",
-           "swdrv_align_hits_pssm"]
+           "swdrv_align_hits_pssm", "swdrv_pssm_from_counts", "swdrv_build_pssm", "swdrv_write_pssm_ascii"]
 
 
 class DriverError(RuntimeError):
@@ -145,6 +145,50 @@ def _pssm_fns():
                          ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
         submit.argtypes = [vp, vp, ctypes.c_int32]
     return scan, submit
+
+
+class _PssmInfo(ctypes.Structure):
+    _fields_ = [("used", ctypes.c_int32), ("below_score", ctypes.c_int32), ("no_trace", ctypes.c_int32),
+                ("copies", ctypes.c_int32), ("lambda_", ctypes.c_double), ("included", ctypes.c_void_p)]
+
+
+def _build_fns():
+    """swdrv_pssm_from_counts / swdrv_build_pssm / swdrv_write_pssm_ascii, bound on first use (like swdrv_align_hits: not in
+    every build of this C ABI)"""
+    fc, bp, wr = lib.swdrv_pssm_from_counts, lib.swdrv_build_pssm, lib.swdrv_write_pssm_ascii
+    if fc.argtypes is None:
+        vp = ctypes.c_void_p
+        fc.argtypes = [ctypes.c_int, vp, ctypes.c_int32, vp, vp, ctypes.c_double, vp, vp, ctypes.POINTER(ctypes.c_double)]
+        bp.argtypes = [vp, ctypes.c_char_p, ctypes.c_int32, vp, vp, vp, ctypes.c_int, ctypes.c_int32, ctypes.c_double, vp,
+                       ctypes.POINTER(_PssmInfo)]
+        wr.argtypes = [ctypes.c_char_p, vp, ctypes.c_int32, ctypes.c_char_p]
+    return fc, bp, wr
+
+
+def pssm_from_counts(master_codes, counts, wcounts, matrix=62, pseudocount=10.0, with_raw=False):
+    """swdrv_pssm_from_counts (no GPU needed): residue counts (qlen x 20, uint32) and weighted counts (qlen x 20, uint64) of a
+    master sequence's aligned hits -> ((qlen, 21) int8 PSSM, lambda), or (PSSM, lambda, raw (qlen, 20) float64 scores)."""
+    m = np.ascontiguousarray(master_codes, dtype=np.int8)
+    qlen = len(m)
+    c = np.ascontiguousarray(counts, dtype=np.uint32)
+    w = np.ascontiguousarray(wcounts, dtype=np.uint64)
+    if qlen < 1 or c.size != qlen * 20 or w.size != qlen * 20:
+        raise ValueError("counts and wcounts must be (qlen, 20) arrays for a master of qlen >= 1 codes")
+    out = np.zeros((qlen, 21), dtype=np.int8)
+    raw = np.zeros((qlen, 20), dtype=np.float64)
+    lam = ctypes.c_double()
+    _check(_build_fns()[0](int(matrix), m.ctypes.data, qlen, c.ctypes.data, w.ctypes.data, float(pseudocount), out.ctypes.data,
+                           raw.ctypes.data, ctypes.byref(lam)))
+    return (out, lam.value, raw) if with_raw else (out, lam.value)
+
+
+def write_pssm_ascii(path, pssm, consensus):
+    """The C++ writer of NCBI ASCII PSSMs (what `align --outPssm` writes; the layout of pssm.write_ascii)."""
+    from . import pssm as _pssm
+    m = _pssm.as_pssm(pssm)
+    if isinstance(consensus, str):
+        consensus = consensus.encode()
+    _check(_build_fns()[2](str(path).encode(), m.ctypes.data, m.shape[0], consensus))
 
 
 # ---- input helpers of the host library (what `align` does to its inputs; no GPU needed) ----
@@ -549,6 +593,50 @@ class Driver:
                                 res.ctypes.data, cigar.ctypes.data, cap))
         cigars = [capi.cigar_string(cigar[int(r["cigar_offset"]):int(r["cigar_offset"]) + int(r["cigar_len"])]) for r in res]
         return res, cigars
+
+    def build_pssm(self, query_letters, result, pssm=None, min_score=0, pseudocount=10.0):
+        """One step of an iterated search (swdrv_build_pssm): the hits of `result` — a scan of `query_letters`, or with
+        `pssm` given a scan_pssm of it, `query_letters` being the master sequence — aligned, filtered (score >= min_score,
+        with a CIGAR, not a copy of the master), accumulated on the GPU and converted.
+        -> ((qlen, 21) int8 PSSM, info dict: used, below_score, no_trace, copies, lambda, included = ids that took part)"""
+        from . import pssm as _pssm
+        if isinstance(query_letters, str):
+            query_letters = query_letters.encode()
+        qlen = len(query_letters)
+        scored_with = None
+        if pssm is not None:
+            scored_with = _pssm.as_pssm(pssm)
+            if scored_with.shape[0] != qlen:
+                raise ValueError("the master has %d residues, the PSSM %d rows" % (qlen, scored_with.shape[0]))
+        ids = np.ascontiguousarray(result["ids"], dtype=np.int64)
+        scores = np.ascontiguousarray(result["scores"], dtype=np.int32)
+        n = len(ids)
+        out = np.zeros((max(qlen, 1), 21), dtype=np.int8)
+        flags = np.zeros(max(n, 1), dtype=np.uint8)
+        info = _PssmInfo(included=flags.ctypes.data)
+        _check(_build_fns()[1](self.handle, query_letters, qlen, scored_with.ctypes.data if scored_with is not None else None,
+                               ids.ctypes.data, scores.ctypes.data, n, int(min_score), float(pseudocount), out.ctypes.data,
+                               ctypes.byref(info)))
+        return out[:qlen], {"used": info.used, "below_score": info.below_score, "no_trace": info.no_trace, "copies": info.copies,
+                            "lambda": info.lambda_, "included": [int(i) for i, f in zip(ids, flags[:n]) if f]}
+
+    def iterate(self, query_letters, rounds, min_score, pseudocount=10.0):
+        """Iterated profile search: round 1 scans with the letters; every round builds a PSSM from its reported hits
+        (build_pssm), and round r + 1 scans with the one of round r.  Stops after `rounds` rounds, or when a round includes
+        the ids the round before included (then the last info has converged = True).
+        -> (result of the last round, PSSM built from it, list of the rounds' info dicts)"""
+        if rounds < 1:
+            raise ValueError("rounds must be at least 1")
+        result = self.scan(query_letters)
+        scoring, infos = None, []
+        while True:
+            built, info = self.build_pssm(query_letters, result, pssm=scoring, min_score=min_score, pseudocount=pseudocount)
+            info["converged"] = bool(infos) and sorted(info["included"]) == sorted(infos[-1]["included"])
+            infos.append(info)
+            if len(infos) >= rounds or info["converged"]:
+                return result, built, infos
+            scoring = built
+            result = self.scan_pssm(scoring)
 
     def reference_length(self, i):
         return int(lib.swdrv_reference_length(self.handle, i))

@@ -2,7 +2,8 @@
 
 A PSSM is a (qlen, 21) int8 array: row i = query position i, column c = dbdata subject code c
 (0..19 = ARNDCQEGHILKMFPSTWYV, 20 = "other" and the padding of the dbdata layout; it must be negative in every row).
-Pure Python / numpy: the scans themselves run in the HIP library (capi.Context.set_query_pssm, driver.Driver.scan_pssm).
+Pure Python / numpy, but for from_counts (the host library's conversion of aligned hits' counts into a PSSM): the scans
+themselves run in the HIP library (capi.Context.set_query_pssm, driver.Driver.scan_pssm).
 """
 import numpy as np
 
@@ -52,6 +53,20 @@ def from_sequence(letters, matrix):
         raise ValueError("query codes must be 0..%d" % (dim - 1))
     cols = list(range(20)) + [23 if dim == 25 else 20]
     return as_pssm(m[codes][:, cols])
+
+
+def from_counts(master, counts, wcounts, matrix=62, pseudocount=10.0, with_raw=False):
+    """The PSSM of a master sequence's aligned hits, from their residue counts and weighted counts (what
+    capi.pssm_accumulate computes on the GPU; DESIGN.md "Building a PSSM").  A thin binding of the host library's
+    swdrv_pssm_from_counts; no GPU needed.
+
+    master: residue string or dbdata codes (20 and above: not a standard residue); counts / wcounts: (qlen, 20) uint32 /
+    uint64; matrix: 45 | 50 | 62 | 80 (or the 25-letter 4525 ...: the 21-letter table of the same name); pseudocount > 0.
+    -> (pssm, lambda), with_raw: (pssm, lambda, (qlen, 20) float64 scores before rounding)"""
+    from . import driver
+    if isinstance(master, (str, bytes)):
+        master = driver.encode(master)
+    return driver.pssm_from_counts(master, counts, wcounts, matrix=matrix, pseudocount=pseudocount, with_raw=with_raw)
 
 
 def consensus_of(pssm):

@@ -190,6 +190,42 @@ int swdrv_align_hits(swdrv* d, const char* query, int32_t qlen, const int64_t* i
 int swdrv_align_hits_pssm(swdrv* d, const int8_t* pssm, int32_t qlen, const char* consensus, const int64_t* ids,
                           const int32_t* scores, int n, sw_align_result* results, uint32_t* cigar, int64_t cigar_cap);
 
+/* Building a PSSM from a query's aligned hits (an extension; DESIGN.md, "Building a PSSM"): the step between two rounds of
+ * an iterated profile search.
+ *
+ * The conversion alone (pure host code, no GPU needed): residue counts and weighted counts, as sw_pssm_accumulate of
+ * include/cudasw4_amd_pssm.h defines them, into the qlen x 21 int8 PSSM every scan takes.  matrix: as for the driver's
+ * constructor; a 25-letter matrix stands for the 21-letter table of the same name.  master_codes: dbdata codes of the
+ * master sequence (20 and above: not a standard residue).  counts (uint32) and wcounts (uint64): qlen x 20.
+ * pseudocount: beta > 0.  raw_out (optional): qlen x 20 doubles, the scores before rounding (rows without counts: the
+ * table's entries).  lambda_out (optional): the matrix's ungapped lambda under the Robinson & Robinson background.
+ * Column 20 of row i is table[min(master_codes[i], 20)][20]; a table where that is not negative is refused. */
+int swdrv_pssm_from_counts(int matrix, const int8_t* master_codes, int32_t qlen, const uint32_t* counts,
+                           const uint64_t* wcounts, double pseudocount, int8_t* pssm_out, double* raw_out, double* lambda_out);
+
+typedef struct swdrv_pssm_info {
+    int32_t used;          /* hits that took part */
+    int32_t below_score;   /* left out: scan score below min_score */
+    int32_t no_trace;      /* left out: SW_ALIGN_NO_TRACE (no CIGAR within the trace budget) */
+    int32_t copies;        /* left out: a copy of the master (the whole query, all columns identical) */
+    double lambda;
+    uint8_t* included;     /* in: NULL, or n bytes that receive 1 for every hit that took part and 0 for the others */
+} swdrv_pssm_info;
+
+/* The whole step: align the n hits `ids` / `scores` of a scan of the master — with its letters when pssm is NULL, else
+ * with `pssm` (qlen x 21 int8, the PSSM the hits were scanned with; the master's letters are the consensus) —, apply the
+ * inclusion rule, accumulate on the device (sw_pssm_accumulate, on the subjects, results and CIGARs the aligner left
+ * there) and convert.  A hit is left out, in this order, when its score is below min_score, when it has no CIGAR within
+ * the trace budget, or when it is a copy of the master (q_begin == 0, q_end == qlen, identities == columns == qlen); hits of
+ * score 0 have no alignment and take no part either.  pssm_out: qlen x 21 int8; info_out: optional. */
+int swdrv_build_pssm(swdrv* d, const char* master_letters, int32_t qlen, const int8_t* pssm, const int64_t* ids,
+                     const int32_t* scores, int n, int32_t min_score, double pseudocount, int8_t* pssm_out,
+                     swdrv_pssm_info* info_out);
+
+/* The 20 standard columns of a qlen x 21 PSSM as an NCBI ASCII PSSM file (what `align --outPssm` writes and `align --pssm`
+ * reads; column 20 is not part of the format).  consensus: qlen residue letters, NUL-terminated.  No GPU needed. */
+int swdrv_write_pssm_ascii(const char* path, const int8_t* pssm, int32_t qlen, const char* consensus);
+
 /* ---- input helpers (no GPU needed): what `align` does to its inputs before the scan ---- */
 
 /* ConvertAA_20 (convert.cuh:6-34): letters -> codes 0..20 */

@@ -51,6 +51,42 @@ int sw_query_is_pssm(const sw_ctx* ctx);
  *   CONTRACT: column 20 of every row negative, as for the PSSM of a scan; the rows are read as they are. */
 int sw_align_hits_pssm(sw_ctx* ctx, const sw_align_args* a, const int8_t* pssm);
 
+/* Building a PSSM: the weighted residue counts of a query's aligned hits ("Building a PSSM").  The n hits are
+ * what sw_align_hits / sw_align_hits_pssm wrote for them (results, CIGAR words) and their subjects; the master sequence
+ * `query` is one more sequence, index n, with residue query[i] at every position i where query[i] < 20.
+ *   A hit takes part when its include byte is non-zero (include == NULL: every hit), its status is SW_ALIGN_OK and its
+ *   cigar_len > 0.  It has residue a at query position i when a '=' or 'X' column of its CIGAR pairs position i with the
+ *   subject code a < 20; 'I' and 'D' columns and subject codes of 20 and above contribute nothing.
+ *   counts[i][a]  (uint32, qlen x 20) = sequences (master included) that have residue a at i; k_i = the a with counts > 0
+ *   weights[h]    (uint64, n + 1)     = sum over the (i, a) of sequence h of floor(2^32 / (k_i * counts[i][a])): position-based
+ *                                       sequence weights (Henikoff & Henikoff 1994) in fixed point; 0 for a hit that takes no part
+ *   wcounts[i][a] (uint64, qlen x 20) = sum of weights[h] over the sequences h that have a at i
+ *   used          (int32)             = hits that took part
+ * Integer arithmetic throughout: the result does not depend on any order of summation.  All pointers are DEVICE pointers;
+ * query may be NULL (no master row), include may be NULL.  The call zeroes its outputs itself and is asynchronous on
+ * `stream`.  n == 0 is legal (the master alone).  SW_ERR_INVALID: qlen < 1, qlen > SW_PSSM_MAX_QUERY_LEN, n < 0, a null
+ * output, or n > 0 with a null chars / offsets / lengths / results / cigar; counts must be 16-byte aligned. */
+typedef struct sw_pssm_accumulate_args {
+    const int8_t* query;         /* master codes, qlen; NULL: no master row */
+    int32_t qlen;
+    int32_t n;                   /* hits */
+    const int8_t* chars;         /* the subjects, as in sw_align_args */
+    const uint64_t* offsets;     /* n + 1 */
+    const int32_t* lengths;      /* n */
+    const sw_align_result* results;   /* n, as the aligner wrote them; cigar_offset is honoured */
+    const uint32_t* cigar;
+    const uint8_t* include;      /* n, or NULL */
+    uint32_t* counts;            /* out: qlen x 20 */
+    uint64_t* weights;           /* out: n + 1, entry n is the master's */
+    uint64_t* wcounts;           /* out: qlen x 20 */
+    int32_t* used;               /* out */
+    void* const* phase_events;   /* HOST, optional: 3 hipEvent_t recorded on `stream` before the memsets and the counting
+                                    launch, between the two launches and after the weighting launch */
+    void* stream;
+} sw_pssm_accumulate_args;
+
+int sw_pssm_accumulate(sw_ctx* ctx, const sw_pssm_accumulate_args* a);
+
 #ifdef __cplusplus
 }
 #endif
