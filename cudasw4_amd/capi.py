@@ -35,6 +35,9 @@ EXPORTS = ["sw_batch_create", "sw_batch_destroy", "sw_scan_batch", "sw_batch_joi
            "sw_align_hits"]
 # ... and include/cudasw4_amd_pssm.h (profile search: a position-specific scoring matrix as the query)
 PSSM_EXPORTS = ["sw_set_query_pssm", "sw_query_is_pssm", "sw_align_hits_pssm", "sw_pssm_accumulate"]
+# ... and include/cudasw4_amd_stats.h (search statistics: the (length bin, score) histogram of a scan's scores)
+STATS_EXPORTS = ["sw_score_histogram"]
+STATS_LBINS, STATS_SBINS = 64, 256
 
 
 # sw_align_hits (include/cudasw4_amd.h): result records, statuses, flags, CIGAR op codes
@@ -133,6 +136,8 @@ def _load():
     if hasattr(L, "sw_set_query_pssm"):
         L.sw_set_query_pssm.argtypes = [vp, vp, i32, vp]
         L.sw_query_is_pssm.argtypes = [vp]
+    if hasattr(L, "sw_score_histogram"):
+        L.sw_score_histogram.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
     return L
 
 
@@ -330,6 +335,16 @@ def pssm_accumulate(ctx, query, qlen, n, chars, offsets, lengths, results, cigar
                             cigar or None, include or None, counts or None, weights or None, wcounts or None, used or None,
                             ctypes.cast(ev, ctypes.c_void_p) if ev is not None else None, stream or None)
     check(f(ctx.handle if ctx is not None else None, ctypes.byref(a)))
+
+
+def score_histogram(ctx, scores, lengths, n, hist, sumlen, skipped, stream=0):
+    """sw_score_histogram (include/cudasw4_amd_stats.h): ADD the n subjects (scores float32, lengths int32) to hist (uint32,
+    64 x 256: [length bin][min(score, 255)]), sumlen (uint64, 64) and skipped (uint32, 1: negative scores, binned nowhere).
+    Every buffer is a device pointer as an integer; the caller zeroes the outputs.  Asynchronous on `stream`."""
+    if not hasattr(lib, "sw_score_histogram"):
+        raise SwError(-1, "this build of libcudasw4_amd.so has no sw_score_histogram")
+    check(lib.sw_score_histogram(ctx.handle if ctx is not None else None, scores or None, lengths or None, n, hist or None,
+                                 sumlen or None, skipped or None, stream or None))
 
 
 def topk_temp_bytes(n, k):

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cctype>
 #include <chrono>
+#include <cstdio>
 #include <cstdlib>
 #include <deque>
 #include <fstream>
@@ -22,6 +23,7 @@
 #include "pssm_build.hpp"
 #include "pssm_query.hpp"
 #include "search_driver.hpp"
+#include "search_stats.hpp"
 #include "sequence_reader.hpp"
 
 using namespace swh;
@@ -41,12 +43,43 @@ struct AlignmentColumns {
     }
 };
 
+// --evalues / --maxEvalue: the fit of one query's scan and what is printed of it (nullptr: no statistics columns)
+struct EvalueReport {
+    SearchStats stats;
+    bool filter = false;     // --maxEvalue: only results with E <= maxE are printed (none where the scan allows no fit)
+    double maxE = 0;
+    HitStatistics of(const ScanResult& r, const SearchDriver& d, size_t i) const {
+        return hit_statistics(stats, r.scores[i], d.getReferenceLength(r.referenceIds[i]));
+    }
+    bool shows(const HitStatistics& h) const { return !filter || (stats.fitted() && h.e <= maxE); }
+    static std::string z_text(const SearchStats& s, const HitStatistics& h) {
+        if (!s.fitted()) return "*";
+        char buf[48];
+        std::snprintf(buf, sizeof buf, "%.2f", h.z);
+        return buf;
+    }
+    static std::string e_text(const SearchStats& s, const HitStatistics& h) {
+        if (!s.fitted()) return "*";
+        char buf[48];
+        std::snprintf(buf, sizeof buf, "%.3g", h.e);
+        return buf;
+    }
+};
+
 // alignments: nullptr without --alignments / --pssmAlignments, else one per result
-void printScanResultPlain(std::ostream& os, const ScanResult& r, const SearchDriver& d, const std::vector<HitAlignment>* alignments = nullptr) {
+void printScanResultPlain(std::ostream& os, const ScanResult& r, const SearchDriver& d, const std::vector<HitAlignment>* alignments = nullptr,
+                          const EvalueReport* ev = nullptr) {
     for (size_t i = 0; i < r.scores.size(); i++) {
         const int64_t id = r.referenceIds[i];
+        HitStatistics hs;
+        if (ev) {
+            hs = ev->of(r, d, i);
+            if (!ev->shows(hs)) continue;
+        }
         os << "Result " << i << ". Score: " << r.scores[i] << ". Length: " << d.getReferenceLength(id) << ". Header "
-           << d.getReferenceHeader(id) << ". referenceId " << id << "\n";
+           << d.getReferenceHeader(id) << ". referenceId " << id;
+        if (ev) os << " Z-score: " << EvalueReport::z_text(ev->stats, hs) << " E-value: " << EvalueReport::e_text(ev->stats, hs);
+        os << "\n";
         if (alignments) {
             const HitAlignment& a = (*alignments)[i];
             const AlignmentColumns c(a.r);
@@ -57,16 +90,22 @@ void printScanResultPlain(std::ostream& os, const ScanResult& r, const SearchDri
     }
 }
 
-void printTSVHeader(std::ostream& os, bool alignments) {
+void printTSVHeader(std::ostream& os, bool alignments, bool evalues) {
     os << "Query number\tQuery length\tQuery header\tResult number\tResult score\tReference length\tReference header\tReference ID in DB";
     if (alignments) os << "\tQuery begin\tQuery end\tReference begin\tReference end\tAlignment length\tIdentities\tGap opens\tCIGAR";
+    if (evalues) os << "\tZ-score\tE-value";
     os << "\n";
 }
 
 void printScanResultTSV(std::ostream& os, const ScanResult& r, const SearchDriver& d, int64_t queryId, int64_t queryLength,
-                        std::string_view queryHeader, const std::vector<HitAlignment>* alignments = nullptr) {
+                        std::string_view queryHeader, const std::vector<HitAlignment>* alignments = nullptr, const EvalueReport* ev = nullptr) {
     for (size_t i = 0; i < r.scores.size(); i++) {
         const int64_t id = r.referenceIds[i];
+        HitStatistics hs;
+        if (ev) {
+            hs = ev->of(r, d, i);
+            if (!ev->shows(hs)) continue;
+        }
         os << queryId << '\t' << queryLength << '\t' << queryHeader << '\t' << i << '\t' << r.scores[i] << '\t'
            << d.getReferenceLength(id) << '\t' << d.getReferenceHeader(id) << '\t' << id;
         if (alignments) {
@@ -75,6 +114,7 @@ void printScanResultTSV(std::ostream& os, const ScanResult& r, const SearchDrive
             os << '\t' << c.qb << '\t' << c.qe << '\t' << c.sb << '\t' << c.se << '\t' << a.r.columns << '\t' << a.r.identities
                << '\t' << a.r.gap_opens << '\t' << cigar_string(a.cigar);
         }
+        if (ev) os << '\t' << EvalueReport::z_text(ev->stats, hs) << '\t' << EvalueReport::e_text(ev->stats, hs);
         os << "\n";
     }
 }
@@ -89,6 +129,29 @@ struct Stopwatch {
 void reportScan(const ProgramOptions& o, const ScanResult& r) {
     if (o.verbose) std::cout << "Done. Scan time: " << r.stats.seconds << " s, " << r.stats.gcups << " GCUPS\n";
     else std::cout << "Done.\n";
+}
+
+// the fit of a scan made with the statistics on (--evalues / --maxEvalue / --inclusionEvalue)
+SearchStats fitOf(const ScanResult& r) {
+    if (r.table.empty()) throw std::runtime_error("internal error: a scan without its score table");
+    return stats_from_table(r.table.front());
+}
+
+void reportStatistics(const ProgramOptions& o, const SearchStats& s) {
+    if (!o.verbose) return;
+    if (!s.fitted()) std::cout << "statistics: no fit\n";
+    else std::cout << "statistics: N " << s.N << " fitted on " << s.nIncluded << " a " << s.a << " b " << s.b1 << " sd " << s.sd
+                   << " rounds " << s.rounds << "\n";
+}
+
+// what the result lines of a query print of its statistics: nullptr without --evalues / --maxEvalue
+const EvalueReport* evalueReport(const ProgramOptions& o, const ScanResult& r, EvalueReport& storage) {
+    if (!o.wantStatistics()) return nullptr;
+    storage.stats = fitOf(r);
+    storage.filter = o.haveMaxEvalue;
+    storage.maxE = o.maxEvalue;
+    reportStatistics(o, storage.stats);
+    return o.reportEvalues() ? &storage : nullptr;
 }
 
 // --iterations / --outPssm: the rounds of one query behind its first scan (pssm_build.hpp; DESIGN.md "Building a PSSM").
@@ -110,8 +173,17 @@ IterationResult runIterations(const ProgramOptions& o, SearchDriver& driver, Pss
     IterationResult out;
     for (int round = 1;; round++) {
         PssmBuildInfo info;
+        // --inclusionEvalue: a result goes in by its E-value under THIS round's fit (none where the scan allows no fit)
+        std::vector<uint8_t> admitted;
+        if (o.haveInclusionEvalue) {
+            const SearchStats st = fitOf(r);
+            admitted.resize(r.scores.size());
+            for (size_t i = 0; i < r.scores.size(); i++)
+                admitted[i] = st.fitted() && hit_statistics(st, r.scores[i], driver.getReferenceLength(r.referenceIds[i])).e <= o.inclusionEvalue;
+        }
         out.built = builder.build(master.data(), qlen, scoring.empty() ? nullptr : scoring.data(), r.referenceIds.data(),
-                                  r.scores.data(), r.scores.size(), o.inclusionScore, o.pseudocount, &info);
+                                  r.scores.data(), r.scores.size(), o.inclusionScore, o.pseudocount, &info,
+                                  o.haveInclusionEvalue ? admitted.data() : nullptr);
         out.alignments = std::move(info.alignments);
         std::vector<int64_t> included;
         for (size_t i = 0; i < info.included.size(); i++)
@@ -120,7 +192,8 @@ IterationResult runIterations(const ProgramOptions& o, SearchDriver& driver, Pss
         const bool converged = round > 1 && included == previous;
         if (o.verbose)
             std::cout << "Query " << queryNum << " round " << round << ": " << r.scores.size() << " results, " << info.used
-                      << " in the PSSM, " << info.belowScore << " below the inclusion score, " << info.noTrace << " without a trace, "
+                      << " in the PSSM, " << info.belowScore << (o.haveInclusionEvalue ? " above the inclusion E-value, " : " below the inclusion score, ")
+                      << info.noTrace << " without a trace, "
                       << info.copies << " copies of the query, lambda " << info.lambda
                       << (converged && round < o.iterations ? ", converged" : "") << "\n";
         if (round >= o.iterations || converged) break;
@@ -175,12 +248,14 @@ void processQueryFile(const std::string& file, const ProgramOptions& o, SearchDr
             if (aligner && iteration) alignments = std::move(rounds.alignments);
             else if (aligner) alignments = aligner->align(q.sequence.data(), int32_t(q.sequence.size()), r);
             const std::vector<HitAlignment>* al = aligner ? &alignments : nullptr;
+            EvalueReport evStorage;
+            const EvalueReport* ev = evalueReport(o, r, evStorage);
             if (o.outputMode == ProgramOptions::OutputMode::Plain) {
                 (interactive ? std::cout : out) << "Query " << q.num << ", header" << q.header << ", length " << q.sequence.size()
                                                 << ", num overflows " << r.stats.numOverflows << "\n";
-                printScanResultPlain(out, r, driver, al);
+                printScanResultPlain(out, r, driver, al, ev);
             } else {
-                printScanResultTSV(out, r, driver, interactive ? -1 : q.num, int64_t(q.sequence.size()), interactive ? "-" : q.header, al);
+                printScanResultTSV(out, r, driver, interactive ? -1 : q.num, int64_t(q.sequence.size()), interactive ? "-" : q.header, al, ev);
             }
             out.flush();
         }
@@ -222,11 +297,13 @@ void processPssmQuery(const PssmQuery& q, const ProgramOptions& o, SearchDriver&
         if (aligner && iteration) alignments = std::move(rounds.alignments);
         else if (aligner) alignments = aligner->align(q.scores.data(), q.length(), q.consensus.data(), r);
         const std::vector<HitAlignment>* al = aligner ? &alignments : nullptr;
+        EvalueReport evStorage;
+        const EvalueReport* ev = evalueReport(o, r, evStorage);
         if (o.outputMode == ProgramOptions::OutputMode::Plain) {
             out << "Query " << 0 << ", header " << q.name << ", length " << q.length() << ", num overflows " << r.stats.numOverflows << "\n";
-            printScanResultPlain(out, r, driver, al);
+            printScanResultPlain(out, r, driver, al, ev);
         } else {
-            printScanResultTSV(out, r, driver, 0, int64_t(q.length()), q.name, al);
+            printScanResultTSV(out, r, driver, 0, int64_t(q.length()), q.name, al, ev);
         }
         out.flush();
     }
@@ -251,9 +328,14 @@ int main(int argc, char** argv) {
         if (!options.pssmFiles.empty() && options.interactive)
             throw std::runtime_error("--pssm cannot be combined with --interactive");
         if (options.iterations < 1) throw std::runtime_error("--iterations must be at least 1");
-        if (options.buildsPssm() && !options.haveInclusionScore)
-            throw std::runtime_error("--iterations above 1 and --outPssm need --inclusionScore S: results go into the PSSM by raw score "
-                                     "(at least S), because this program has no E-values");
+        if (options.haveInclusionScore && options.haveInclusionEvalue)
+            throw std::runtime_error("--inclusionScore and --inclusionEvalue cannot be combined: results go into the PSSM by one rule");
+        if (options.buildsPssm() && !options.haveInclusionScore && !options.haveInclusionEvalue)
+            throw std::runtime_error("--iterations above 1 and --outPssm need --inclusionScore S (results go into the PSSM by raw score, "
+                                     "at least S) or --inclusionEvalue X (by their E-values, at most X)");
+        if (options.haveMaxEvalue && !(options.maxEvalue >= 0)) throw std::runtime_error("--maxEvalue must not be negative");
+        if (options.haveInclusionEvalue && !(options.inclusionEvalue >= 0)) throw std::runtime_error("--inclusionEvalue must not be negative");
+        if (options.wantStatistics() && options.interactive) throw std::runtime_error("--evalues / --maxEvalue / --inclusionEvalue cannot be combined with --interactive");
         if (!(options.pseudocount > 0)) throw std::runtime_error("--pseudocount must be positive");
         if (options.buildsPssm() && options.interactive) throw std::runtime_error("--iterations / --outPssm cannot be combined with --interactive");
         if (options.buildsPssm() && options.numTopOutputs < 1) throw std::runtime_error("--iterations / --outPssm need --top of at least 1: the PSSM is built from the reported results");
@@ -279,7 +361,7 @@ int main(int argc, char** argv) {
         }
         std::ofstream outputfile(options.outputfile);
         if (!outputfile) throw std::runtime_error("Cannot open file " + options.outputfile);
-        if (options.outputMode == ProgramOptions::OutputMode::TSV) printTSVHeader(outputfile, options.reportAlignments());
+        if (options.outputMode == ProgramOptions::OutputMode::TSV) printTSVHeader(outputfile, options.reportAlignments(), options.reportEvalues());
 
         SearchDriver driver(deviceIds, options.numTopOutputs, options.matrix, options.kernels, options.memory, options.verbose,
                             options.effectiveGop(), options.effectiveGex());
@@ -303,6 +385,7 @@ int main(int argc, char** argv) {
             if (options.printLengthPartitions) driver.printDBLengthPartitions();
         }
         if (options.loadFullDBToGpu) driver.prefetchDBToGpus();
+        if (options.wantStatistics()) enable_statistics(driver, true);
         std::unique_ptr<HitAligner> aligner;
         if (options.reportAlignments() || options.buildsPssm()) aligner = std::make_unique<HitAligner>(driver);
         std::unique_ptr<PssmBuilder> iteration;   // (non-null: every query goes through its rounds)

@@ -36,7 +36,10 @@ void printOptions(const ProgramOptions& o) {
     if (o.pssmAlignments) std::cout << "pssmAlignments: " << o.pssmAlignments << "\n";
     if (o.iterations != 1) std::cout << "iterations: " << o.iterations << "\n";
     if (o.haveInclusionScore) std::cout << "inclusionScore: " << o.inclusionScore << "\n";
+    if (o.haveInclusionEvalue) std::cout << "inclusionEvalue: " << o.inclusionEvalue << "\n";
     if (o.pseudocount != 10.0) std::cout << "pseudocount: " << o.pseudocount << "\n";
+    if (o.reportEvalues()) std::cout << "evalues: 1\n";
+    if (o.haveMaxEvalue) std::cout << "maxEvalue: " << o.maxEvalue << "\n";
     if (!o.outPssm.empty()) std::cout << "outPssm: " << o.outPssm << "\n";
     std::cout << "blosum: " << substitution_matrix(o.matrix).name << "\n";
     std::cout << "singlePassType: " << to_string(o.kernels.singlePassType) << "\n";
@@ -78,6 +81,9 @@ bool parseArgs(int argc, char** argv, ProgramOptions& o) {
         else if (arg == "--pssmAlignments") o.pssmAlignments = true;
         else if (arg == "--iterations") o.iterations = std::atoi(value(i).c_str());
         else if (arg == "--inclusionScore") { o.inclusionScore = std::atoi(value(i).c_str()); o.haveInclusionScore = true; }
+        else if (arg == "--inclusionEvalue") { o.inclusionEvalue = std::atof(value(i).c_str()); o.haveInclusionEvalue = true; }
+        else if (arg == "--evalues") o.evalues = true;
+        else if (arg == "--maxEvalue") { o.maxEvalue = std::atof(value(i).c_str()); o.haveMaxEvalue = true; }
         else if (arg == "--pseudocount") o.pseudocount = std::atof(value(i).c_str());
         else if (arg == "--outPssm") o.outPssm = value(i);
         else if (arg == "--printLengthPartitions") o.printLengthPartitions = true;
@@ -148,10 +154,16 @@ void printHelp(char** argv) {
     std::cout << "   Iterated profile search\n";
     std::cout << "      --iterations N : N rounds per query (N >= 1, default 1). Round r + 1 scans with the PSSM built from the results of round r\n"
                  "        (the --top list); the results printed are the last round's. Stops early when the set of included results repeats.\n";
-    std::cout << "      --inclusionScore S : Results with a raw score of at least S go into the PSSM (there are no E-values). Mandatory with\n"
-                 "        --iterations above 1 and with --outPssm.\n";
+    std::cout << "      --inclusionScore S : Results with a raw score of at least S go into the PSSM. --iterations above 1 and --outPssm need\n"
+                 "        this option or --inclusionEvalue, not both.\n";
+    std::cout << "      --inclusionEvalue X : Results with an E-value of at most X, under the statistics of the round's own scan, go into the PSSM.\n";
     std::cout << "      --pseudocount B : Weight of the substitution-matrix pseudo-frequencies, B > 0. Default val = " << d.pseudocount << "\n";
     std::cout << "      --outPssm PREFIX : Write the PSSM built from the last round's results to PREFIX.<query number>.pssm (NCBI ASCII, as --pssm reads)\n\n";
+    std::cout << "   Search statistics\n";
+    std::cout << "      --evalues : Report a Z-score and an E-value with every result: the scores of the whole scan are regressed on the\n"
+                 "        logarithm of the subject length (as FASTA / SSEARCH do), fitted per query on the GPU's score histogram. Two more TSV\n"
+                 "        columns behind all others; '*' where the scan allows no fit (fewer than 100 usable scores, or no spread).\n";
+    std::cout << "      --maxEvalue X : Implies --evalues. Print only the results of the --top list with an E-value of at most X.\n\n";
     std::cout << "   Memory\n";
     std::cout << "      --maxGpuMem val : Try not to use more than val bytes of gpu memory per gpu. Uses all available gpu memory by default\n";
     std::cout << "      --maxTempBytes val : Size of temp storage in GPU memory. Can use suffix K,M,G. Default val = " << d.memory.maxTempBytes << "\n";

@@ -26,7 +26,7 @@ struct ProgramOptions {
     bool pssmAlignments = false;
     bool reportAlignments() const { return alignments || pssmAlignments; }
     // Iterated profile search (pssm_build.hpp; an extension): --iterations N rounds, each scanning with the PSSM built from
-    // the round before's reported hits of raw score >= --inclusionScore (there are no E-values); --pseudocount is the
+    // the round before's reported hits of raw score >= --inclusionScore (or by E-value: --inclusionEvalue below); --pseudocount is the
     // conversion's beta; --outPssm PREFIX writes PREFIX.<query number>.pssm
     int iterations = 1;
     bool haveInclusionScore = false;
@@ -34,6 +34,16 @@ struct ProgramOptions {
     double pseudocount = 10.0;
     std::string outPssm;
     bool buildsPssm() const { return iterations > 1 || !outPssm.empty(); }
+    // Search statistics (search_stats.hpp; an extension): --evalues reports a Z-score and an E-value with every result;
+    // --maxEvalue X (implies --evalues) prints only the results with E <= X; --inclusionEvalue X takes the place of
+    // --inclusionScore: results go into the PSSM by their E-value under the round's own fit
+    bool evalues = false;
+    bool haveMaxEvalue = false;
+    double maxEvalue = 0;
+    bool haveInclusionEvalue = false;
+    double inclusionEvalue = 0;
+    bool reportEvalues() const { return evalues || haveMaxEvalue; }
+    bool wantStatistics() const { return reportEvalues() || haveInclusionEvalue; }
     bool prefetchDBFile = false;
     int numTopOutputs = 10;
     int gop = -11;

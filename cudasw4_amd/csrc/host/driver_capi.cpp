@@ -134,6 +134,7 @@ int swdrv_scan(swdrv* d, const char* query, int32_t qlen, int32_t* scores, int64
         if (nres) *nres = n;
         if (num_overflows) *num_overflows = r.stats.numOverflows;
         d->lastRescored = r.stats.numRescored;
+        d->lastTable = std::move(r.table);
         if (seconds) *seconds = r.stats.seconds;
         if (gcups) *gcups = r.stats.gcups;
     });
@@ -155,6 +156,7 @@ int swdrv_scan_collect(swdrv* d, int32_t* scores, int64_t* ids, int cap, int* nr
         if (nres) *nres = n;
         if (num_overflows) *num_overflows = r.stats.numOverflows;
         d->lastRescored = r.stats.numRescored;
+        d->lastTable = std::move(r.table);
         if (seconds) *seconds = r.stats.seconds;
         if (gcups) *gcups = r.stats.gcups;
     });

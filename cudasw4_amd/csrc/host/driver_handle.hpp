@@ -11,6 +11,7 @@ struct swdrv {
     std::unique_ptr<swh::SearchDriver> driver;
     std::shared_ptr<swh::Database> db;
     int lastRescored = 0;
+    std::vector<swh::ScoreTable> lastTable;   // ScanResult::table of the query collected last (search_stats.cpp)
 };
 
 namespace swh {

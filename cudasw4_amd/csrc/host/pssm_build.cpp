@@ -118,7 +118,8 @@ void* PssmBuilder::grow(int slot, size_t bytes) {
 }
 
 std::vector<int8_t> PssmBuilder::build(const char* master, int32_t qlen, const int8_t* pssm, const int64_t* ids,
-                                       const int32_t* scores, size_t n, int32_t minScore, double pseudocount, PssmBuildInfo* info) {
+                                       const int32_t* scores, size_t n, int32_t minScore, double pseudocount, PssmBuildInfo* info,
+                                       const uint8_t* admitted) {
     if (qlen < 1 || !master) throw std::runtime_error("PSSM build: empty master sequence");
     if (qlen > (1 << 20)) throw std::runtime_error("PSSM build: queries longer than 2^20 residues are not supported");
     if (n > 0 && (!ids || !scores)) throw std::runtime_error("PSSM build: null hit list");
@@ -134,7 +135,7 @@ std::vector<int8_t> PssmBuilder::build(const char* master, int32_t qlen, const i
     int32_t expectUsed = 0;
     for (size_t h = 0; h < n; h++) {
         const sw_align_result& r = I.alignments[h].r;
-        if (scores[h] < minScore) I.belowScore++;
+        if (admitted ? !admitted[h] : scores[h] < minScore) I.belowScore++;
         else if (r.status == SW_ALIGN_NO_TRACE) I.noTrace++;
         else if (r.status == SW_ALIGN_OK && r.q_begin == 0 && r.q_end == qlen && r.identities == qlen && r.columns == qlen) I.copies++;
         else if (r.status == SW_ALIGN_OK && r.cigar_len > 0) {

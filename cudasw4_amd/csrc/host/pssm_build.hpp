@@ -45,9 +45,10 @@ public:
     PssmBuilder& operator=(const PssmBuilder&) = delete;
 
     // master: the original query's letters (for a PSSM input the residue column of its file).  pssm: nullptr when the hits
-    // were scanned with the letters, else the qlen x 21 PSSM they were scanned with.  -> qlen x 21 int8
+    // were scanned with the letters, else the qlen x 21 PSSM they were scanned with.  admitted: nullptr, or one byte per hit
+    // that takes the place of the score test (inclusion by E-value: 0 = left out, counted in belowScore).  -> qlen x 21 int8
     std::vector<int8_t> build(const char* master, int32_t qlen, const int8_t* pssm, const int64_t* ids, const int32_t* scores,
-                              size_t n, int32_t minScore, double pseudocount, PssmBuildInfo* info);
+                              size_t n, int32_t minScore, double pseudocount, PssmBuildInfo* info, const uint8_t* admitted = nullptr);
 
 private:
     void* grow(int slot, size_t bytes);

@@ -336,11 +336,17 @@ struct SearchDriver::Gpu {
         int top = 0;
         bool used = false;         // this GPU took part in the scan (its shard is not empty)
         int lane = 0;              // whose score arrays the scan filled (Gpu::Lane)
+        // score tap (SearchDriver::setScoreTap): the query's table on the device and its pinned copy; allocated with the
+        // first tapped query that uses the slot
+        ScoreTable* d_table = nullptr;
+        ScoreTable* h_table = nullptr;
+        bool tapped = false;
     };
     ResultSlot res[SearchDriver::kMaxInFlight];
     int lastTop = 0;
     const float* lastTopS = nullptr;   // the finished slot's lists (valid until that slot is reused)
     const int32_t* lastTopI = nullptr;
+    const ScoreTable* lastTable = nullptr;   // the finished slot's table (nullptr: the query was not tapped on this GPU)
     int lastOverflows = 0;      // subjects of the last query whose exact score reached the packed kind's limit (the reference's statistic)
     int lastRescored = 0;       // subjects the packed launches flagged and the 32-bit kind re-scored (>= lastOverflows)
     int32_t qlen = 0;
@@ -491,6 +497,7 @@ SearchDriver::~SearchDriver() {
         for (auto& r : g.res) {
             if (r.done) (void)hipEventDestroy(r.done);
             (void)hipHostFree(r.h_topS); (void)hipHostFree(r.h_topI); (void)hipHostFree(r.h_ovf);
+            (void)hipFree(r.d_table); (void)hipHostFree(r.h_table);
         }
         for (auto* v : {&g.timed, &g.freeTimed})
             for (TimedLaunch& t : *v) { (void)hipEventDestroy(t.ev0); (void)hipEventDestroy(t.ev1); }
@@ -1165,6 +1172,7 @@ void SearchDriver::enqueueOnGpu(Gpu& g, int32_t queryLength, int k, int slot, bo
     rs.top = 0;
     rs.ncounters = 0;
     rs.lane = 0;
+    rs.tapped = false;
     g.spanBegin = g.spanEnd = now_seconds() - scanT0_;
     if (g.numLocal == 0) return;
     TraceRange traceGpu("enqueue on GPU %d: query of %d residues, %ld subjects", g.device, int(queryLength), long(g.numLocal));
@@ -1210,6 +1218,16 @@ void SearchDriver::enqueueOnGpu(Gpu& g, int32_t queryLength, int k, int slot, bo
         }
         if (!g.batches.empty()) scanStreamed(g);
         join_aux(g);
+        // the score tap: every launch that writes scores — streamed batches, windows, re-score, pipelines — has joined
+        if (scoreTap_) {
+            if (!rs.d_table) HIPCHECK(hipMalloc(&rs.d_table, sizeof(ScoreTable)));
+            if (!rs.h_table) HIPCHECK(hipHostMalloc(&rs.h_table, sizeof(ScoreTable)));
+            HIPCHECK(hipMemsetAsync(rs.d_table, 0, sizeof(ScoreTable), g.stream));
+            if (scoreTap_(g.ctx, g.d_scores, g.d_lengths, int64_t(g.numLocal), rs.d_table, g.stream) != 0)
+                throw std::runtime_error(std::string("score tap: ") + sw_last_error());
+            HIPCHECK(hipMemcpyAsync(rs.h_table, rs.d_table, sizeof(ScoreTable), hipMemcpyDeviceToHost, g.stream));
+            rs.tapped = true;
+        }
         const int kk = int(std::min<size_t>(size_t(std::max(k, 0)), g.numLocal));
         if (kk > 0) {
             if (kk > g.topCapacity) {
@@ -1340,6 +1358,7 @@ void SearchDriver::finishOnGpu(Gpu& g, int slot, int32_t qlen) {
     g.lastTopS = rs.h_topS;
     g.lastTopI = rs.h_topI;
     g.resultLane = rs.lane;
+    g.lastTable = nullptr;
     if (!rs.used) return;
     g.use();
     waitForScan(g, rs.done, qlen);
@@ -1365,6 +1384,7 @@ void SearchDriver::finishOnGpu(Gpu& g, int slot, int32_t qlen) {
         throw std::runtime_error("scan failed: " + std::to_string(failed) +
                                  " pipeline stage(s) of a long subject gave up waiting for their neighbour (sw_scan_rows_pipelined)");
     g.lastTop = rs.top;
+    if (rs.tapped) g.lastTable = rs.h_table;
     // how much recent scans re-scored arms and sizes the re-score service of the lane's engine
     if (sw_batch* e = rs.lane == 1 ? (g.laneSwapped ? g.eng : g.lane1.eng) : (g.laneSwapped ? g.lane1.eng : g.eng)) SWCHECK(sw_batch_feedback(e, int32_t(std::max<int64_t>(0, int64_t(g.lastRescored) - dirty))));
     rs.used = false;
@@ -1388,6 +1408,11 @@ void SearchDriver::submitWith(QueryInstallFn install, const int8_t* data, size_t
     submitEncoded(queryLength);
 }
 
+void SearchDriver::setScoreTap(ScoreTapFn tap) {
+    if (pendingCount_) throw std::runtime_error("setScoreTap with queries in flight: collect() them first");
+    scoreTap_ = tap;
+}
+
 void SearchDriver::submit(const char* query, int32_t queryLength) {
     check_submit(db_.get(), queryLength, pendingCount_);
     encodedQuery_.resize(size_t(queryLength));
@@ -1406,6 +1431,7 @@ void SearchDriver::submitEncoded(int32_t queryLength) {
     ps.qlen = queryLength;
     ps.k = numTop_;
     ps.t0 = now_seconds();
+    ps.tapped = scoreTap_ != nullptr;
     if (pendingCount_ == 0) scanT0_ = ps.t0;
     const int slot = ps.slot, k = ps.k;
     const bool inFlight = pendingCount_ > 0;
@@ -1440,6 +1466,18 @@ ScanResult SearchDriver::collect() {
     std::sort(hits.begin(), hits.end(), [](const Hit& a, const Hit& b) { return a.score != b.score ? a.score > b.score : a.id < b.id; });
     if (int(hits.size()) > ps.k) hits.resize(size_t(std::max(ps.k, 0)));
     for (const Hit& h : hits) { result.scores.push_back(h.score); result.referenceIds.push_back(h.id); }
+    if (ps.tapped) {   // integer tables: the sum over the GPUs is the table of the whole DB, in any order
+        result.table.emplace_back();
+        ScoreTable& sum = result.table.back();
+        std::memset(&sum, 0, sizeof sum);
+        for (auto& gp : gpus_) {
+            const ScoreTable* t = gp->lastTable;
+            if (!t) continue;
+            for (size_t i = 0; i < sizeof sum.hist / sizeof sum.hist[0]; i++) sum.hist[i] += t->hist[i];
+            for (int b = 0; b < kStatsLengthBins; b++) sum.sumlen[b] += t->sumlen[b];
+            sum.skipped += t->skipped;
+        }
+    }
 
     // a query's time runs from its submission, or from the end of the query before it when it had to queue behind that
     const double t1 = now_seconds();

@@ -53,10 +53,22 @@ struct BenchmarkStats {  // cudasw4.cuh:75-80
     double gcups = 0;
 };
 
+// The (length bin, score) histogram of every score of a scan: what the search statistics are fitted on (search_stats.hpp,
+// DESIGN.md §12).  Also the layout of the device block a score tap (SearchDriver::setScoreTap) adds into.
+constexpr int kStatsLengthBins = 64, kStatsScoreBins = 256;
+struct ScoreTable {
+    uint32_t hist[kStatsLengthBins * kStatsScoreBins];   // [length bin][min(score, 255)]
+    uint64_t sumlen[kStatsLengthBins];                   // true lengths of the subjects of each length bin
+    uint32_t skipped;                                    // negative scores: binned nowhere
+    uint32_t reserved;
+};
+
 struct ScanResult {  // cudasw4.cuh:82-86
     std::vector<int> scores;
     std::vector<int64_t> referenceIds;
     BenchmarkStats stats;
+    // with a score tap: the tables of all GPUs summed (one element); empty without
+    std::vector<ScoreTable> table;
 };
 
 // One launch of the scan kernel: a run of adjacent length partitions that use the same arithmetic kind.
@@ -194,6 +206,15 @@ public:
     // function lives in the caller's translation unit, so this file needs no entry point of the library beyond the boundary.
     using QueryInstallFn = int (*)(sw_ctx* ctx, const int8_t* data, int32_t queryLength, void* stream);
     void submitWith(QueryInstallFn install, const int8_t* data, size_t bytes, int32_t queryLength);
+    // Score tap: when set, every query submitted from now on calls `tap` on each GPU's work stream right before that
+    // query's top-K, with the final scores of the GPU's shard (the lane's array the query used), the shard's true lengths
+    // (both DEVICE, n entries, shard order) and a zeroed DEVICE block of sizeof(ScoreTable) bytes of the query's own;
+    // collect() copies the blocks back and sums them over the GPUs into ScanResult::table.  Like QueryInstallFn the
+    // function lives in the caller's translation unit (search_stats.cpp: sw_score_histogram).  nullptr: off — nothing is
+    // allocated, launched or copied.  Not with queries in flight.
+    using ScoreTapFn = int (*)(sw_ctx* ctx, const float* scores, const int32_t* lengths, int64_t n, void* deviceOut, void* stream);
+    void setScoreTap(ScoreTapFn tap);
+    bool hasScoreTap() const { return scoreTap_ != nullptr; }
     ScanResult collect();
     int inFlight() const { return int(pendingCount_); }
 
@@ -287,10 +308,11 @@ private:
     std::vector<std::pair<const int8_t*, size_t>> registered_;  // what hipHostRegister was given
     std::vector<int8_t> encodedQuery_;
     QueryInstallFn queryInstall_ = nullptr;   // submitWith: what installs encodedQuery_ (nullptr: sw_set_query)
+    ScoreTapFn scoreTap_ = nullptr;
     double scanT0_ = 0;
     double watchdogSeconds_ = 60.0;   // CUDASW4_AMD_WATCHDOG_SECONDS: base of collect()'s deadline (0: none)
     // queries submitted and not yet collected, oldest first (a ring of kMaxInFlight result slots per GPU)
-    struct PendingScan { int slot = 0; int32_t qlen = 0; int k = 0; double t0 = 0; };
+    struct PendingScan { int slot = 0; int32_t qlen = 0; int k = 0; double t0 = 0; bool tapped = false; };
     PendingScan pending_[kMaxInFlight];
     size_t pendingHead_ = 0, pendingCount_ = 0;
     int nextSlot_ = 0;

@@ -24,7 +24,8 @@ EXPORTS = ["swdrv_last_error", "swdrv_create", "swdrv_destroy", "swdrv_open_db",
            "swdrv_bind_to_numa_node", "swdrv_device_numa_node", "swdrv_window_stats", "swdrv_service_launches",
            "swdrv_tail_overlaps", "swdrv_prefers_two_in_flight", "swdrv_pipeline_launches", "swdrv_handshake_active", "swdrv_preferred_in_flight",
            "swdrv_latency_scans", "swdrv_plan_runs_mode", "swdrv_align_hits", "swdrv_scan_pssm", "swdrv_scan_submit_pssm",
-           "swdrv_align_hits_pssm", "swdrv_pssm_from_counts", "swdrv_build_pssm", "swdrv_write_pssm_ascii"]
+           "swdrv_align_hits_pssm", "swdrv_pssm_from_counts", "swdrv_build_pssm", "swdrv_write_pssm_ascii",
+           "swdrv_set_statistics", "swdrv_last_statistics", "swdrv_stats_from_histogram", "swdrv_evalues", "swdrv_length_bin"]
 
 
 class DriverError(RuntimeError):
@@ -163,6 +164,40 @@ def _build_fns():
                        ctypes.POINTER(_PssmInfo)]
         wr.argtypes = [ctypes.c_char_p, vp, ctypes.c_int32, ctypes.c_char_p]
     return fc, bp, wr
+
+
+STATS_OK, STATS_NO_FIT = 0, 1
+STATS_LBINS, STATS_SBINS = 64, 256
+
+
+class _Stats(ctypes.Structure):
+    _fields_ = [("a", ctypes.c_double), ("b1", ctypes.c_double), ("sd", ctypes.c_double), ("n_included", ctypes.c_int64),
+                ("N", ctypes.c_int64), ("rounds", ctypes.c_int32), ("status", ctypes.c_int32)]
+
+
+def _stats_fns():
+    """swdrv_set_statistics / swdrv_last_statistics / swdrv_stats_from_histogram / swdrv_evalues / swdrv_length_bin, bound on
+    first use (like swdrv_align_hits: not in every build of this C ABI)"""
+    on, last, fit, ev, lb = (lib.swdrv_set_statistics, lib.swdrv_last_statistics, lib.swdrv_stats_from_histogram,
+                             lib.swdrv_evalues, lib.swdrv_length_bin)
+    if on.argtypes is None:
+        vp = ctypes.c_void_p
+        on.argtypes = [vp, ctypes.c_int]
+        last.argtypes = [vp, ctypes.POINTER(_Stats), vp, vp]
+        fit.argtypes = [vp, vp, ctypes.POINTER(_Stats)]
+        ev.argtypes = [ctypes.POINTER(_Stats), vp, vp, ctypes.c_int, vp, vp]
+        lb.argtypes = [ctypes.c_int32]
+    return on, last, fit, ev, lb
+
+
+def _stats_dict(s):
+    return {"a": s.a, "b1": s.b1, "sd": s.sd, "n_included": int(s.n_included), "N": int(s.N), "rounds": int(s.rounds),
+            "status": int(s.status)}
+
+
+def _stats_struct(stats):
+    return _Stats(float(stats["a"]), float(stats["b1"]), float(stats["sd"]), int(stats["n_included"]), int(stats["N"]),
+                  int(stats["rounds"]), int(stats["status"]))
 
 
 def pssm_from_counts(master_codes, counts, wcounts, matrix=62, pseudocount=10.0, with_raw=False):
@@ -324,6 +359,38 @@ class Driver:
                                 ctypes.byref(h)))
         self.handle = h
         self.num_top = num_top
+        self.statistics = False
+
+    def set_statistics(self, on=True):
+        """Search statistics: from now on every scan also histograms its scores on the GPU, and the dicts of
+        scan / scan_pssm / collect carry "zscores" and "evalues" (float64, aligned with "scores") and "stats" (the fit: a, b1,
+        sd, n_included, N, rounds, status; plus the table: hist, sumlen).  Not with queries in flight."""
+        _check(_stats_fns()[0](self.handle, int(bool(on))))
+        self.statistics = bool(on)
+
+    def last_statistics(self):
+        """Fit and table of the query collected last (swdrv_last_statistics) -> the "stats" dict of its result."""
+        s = _Stats()
+        hist = np.zeros((STATS_LBINS, STATS_SBINS), dtype=np.uint32)
+        sumlen = np.zeros(STATS_LBINS, dtype=np.uint64)
+        _check(_stats_fns()[1](self.handle, ctypes.byref(s), hist.ctypes.data, sumlen.ctypes.data))
+        out = _stats_dict(s)
+        out["hist"], out["sumlen"] = hist, sumlen
+        return out
+
+    def _with_statistics(self, result):
+        if not self.statistics:
+            return result
+        st = self.last_statistics()
+        ids = result["ids"]
+        lengths = np.array([self.reference_length(int(i)) for i in ids], dtype=np.int32)
+        z = np.zeros(len(ids), dtype=np.float64)
+        e = np.zeros(len(ids), dtype=np.float64)
+        sc = np.ascontiguousarray(result["scores"], dtype=np.int32)
+        c = _stats_struct(st)
+        _check(_stats_fns()[3](ctypes.byref(c), sc.ctypes.data, lengths.ctypes.data, len(ids), z.ctypes.data, e.ctypes.data))
+        result["zscores"], result["evalues"], result["stats"] = z, e, st
+        return result
 
     def close(self):
         if self.handle:
@@ -480,9 +547,9 @@ class Driver:
         _check(lib.swdrv_scan(self.handle, query_letters, len(query_letters), scores.ctypes.data, ids.ctypes.data, cap,
                               ctypes.byref(nres), ctypes.byref(novf), ctypes.byref(sec), ctypes.byref(gcups)))
         n = nres.value
-        return {"scores": scores[:n].copy(), "ids": ids[:n].copy(), "num_overflows": novf.value,
-                "num_rescored": int(lib.swdrv_last_rescored(self.handle)),
-                "seconds": sec.value, "gcups": gcups.value}
+        return self._with_statistics({"scores": scores[:n].copy(), "ids": ids[:n].copy(), "num_overflows": novf.value,
+                                      "num_rescored": int(lib.swdrv_last_rescored(self.handle)),
+                                      "seconds": sec.value, "gcups": gcups.value})
 
     def scan_pssm(self, pssm):
         """scan() with a position-specific scoring matrix as the query: (qlen, 21) int8, row i = query position i, column c =
@@ -497,9 +564,9 @@ class Driver:
         _check(_pssm_fns()[0](self.handle, m.ctypes.data, m.shape[0], scores.ctypes.data, ids.ctypes.data, cap,
                               ctypes.byref(nres), ctypes.byref(novf), ctypes.byref(sec), ctypes.byref(gcups)))
         n = nres.value
-        return {"scores": scores[:n].copy(), "ids": ids[:n].copy(), "num_overflows": novf.value,
-                "num_rescored": int(lib.swdrv_last_rescored(self.handle)),
-                "seconds": sec.value, "gcups": gcups.value}
+        return self._with_statistics({"scores": scores[:n].copy(), "ids": ids[:n].copy(), "num_overflows": novf.value,
+                                      "num_rescored": int(lib.swdrv_last_rescored(self.handle)),
+                                      "seconds": sec.value, "gcups": gcups.value})
 
     def submit_pssm(self, pssm):
         """submit() with a PSSM query; collect() returns its results.  May be in flight together with a letter query."""
@@ -523,9 +590,9 @@ class Driver:
         _check(lib.swdrv_scan_collect(self.handle, scores.ctypes.data, ids.ctypes.data, cap, ctypes.byref(nres),
                                       ctypes.byref(novf), ctypes.byref(sec), ctypes.byref(gcups)))
         n = nres.value
-        return {"scores": scores[:n].copy(), "ids": ids[:n].copy(), "num_overflows": novf.value,
-                "num_rescored": int(lib.swdrv_last_rescored(self.handle)),
-                "seconds": sec.value, "gcups": gcups.value}
+        return self._with_statistics({"scores": scores[:n].copy(), "ids": ids[:n].copy(), "num_overflows": novf.value,
+                                      "num_rescored": int(lib.swdrv_last_rescored(self.handle)),
+                                      "seconds": sec.value, "gcups": gcups.value})
 
     def scan_many(self, queries):
         """Every query of a list, pipelined: the next query is submitted before the current one is collected, so the
@@ -594,12 +661,24 @@ class Driver:
         cigars = [capi.cigar_string(cigar[int(r["cigar_offset"]):int(r["cigar_offset"]) + int(r["cigar_len"])]) for r in res]
         return res, cigars
 
-    def build_pssm(self, query_letters, result, pssm=None, min_score=0, pseudocount=10.0):
+    def build_pssm(self, query_letters, result, pssm=None, min_score=0, pseudocount=10.0, max_evalue=None):
         """One step of an iterated search (swdrv_build_pssm): the hits of `result` — a scan of `query_letters`, or with
         `pssm` given a scan_pssm of it, `query_letters` being the master sequence — aligned, filtered (score >= min_score,
         with a CIGAR, not a copy of the master), accumulated on the GPU and converted.
+        max_evalue: in place of the min_score test a hit takes part when its E-value under the fit of `result`'s own scan is
+        at most max_evalue (`result` must come from a scan with set_statistics(True); under NO_FIT no hit takes part); the
+        other rules are unchanged, and info's below_score counts the hits the E-value left out.
         -> ((qlen, 21) int8 PSSM, info dict: used, below_score, no_trace, copies, lambda, included = ids that took part)"""
         from . import pssm as _pssm
+        if max_evalue is not None:
+            if "evalues" not in result:
+                raise ValueError("max_evalue needs a result with E-values: set_statistics(True) before the scan")
+            ev = np.asarray(result["evalues"])
+            keep = (ev >= 0) & (ev <= float(max_evalue))
+            kept = {"ids": np.asarray(result["ids"])[keep], "scores": np.asarray(result["scores"])[keep]}
+            built, info = self.build_pssm(query_letters, kept, pssm=pssm, min_score=0, pseudocount=pseudocount)
+            info["below_score"] += int(len(keep) - keep.sum())
+            return built, info
         if isinstance(query_letters, str):
             query_letters = query_letters.encode()
         qlen = len(query_letters)
@@ -620,17 +699,21 @@ class Driver:
         return out[:qlen], {"used": info.used, "below_score": info.below_score, "no_trace": info.no_trace, "copies": info.copies,
                             "lambda": info.lambda_, "included": [int(i) for i, f in zip(ids, flags[:n]) if f]}
 
-    def iterate(self, query_letters, rounds, min_score, pseudocount=10.0):
+    def iterate(self, query_letters, rounds, min_score=0, pseudocount=10.0, max_evalue=None):
         """Iterated profile search: round 1 scans with the letters; every round builds a PSSM from its reported hits
         (build_pssm), and round r + 1 scans with the one of round r.  Stops after `rounds` rounds, or when a round includes
-        the ids the round before included (then the last info has converged = True).
+        the ids the round before included (then the last info has converged = True).  max_evalue: hits go in by their
+        E-value under each round's own fit instead of by min_score (needs set_statistics(True)).
         -> (result of the last round, PSSM built from it, list of the rounds' info dicts)"""
         if rounds < 1:
             raise ValueError("rounds must be at least 1")
+        if max_evalue is not None and not self.statistics:
+            raise ValueError("max_evalue needs set_statistics(True)")
         result = self.scan(query_letters)
         scoring, infos = None, []
         while True:
-            built, info = self.build_pssm(query_letters, result, pssm=scoring, min_score=min_score, pseudocount=pseudocount)
+            built, info = self.build_pssm(query_letters, result, pssm=scoring, min_score=min_score, pseudocount=pseudocount,
+                                          max_evalue=max_evalue)
             info["converged"] = bool(infos) and sorted(info["included"]) == sorted(infos[-1]["included"])
             infos.append(info)
             if len(infos) >= rounds or info["converged"]:

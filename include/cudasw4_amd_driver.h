@@ -226,6 +226,45 @@ int swdrv_build_pssm(swdrv* d, const char* master_letters, int32_t qlen, const i
  * reads; column 20 is not part of the format).  consensus: qlen residue letters, NUL-terminated.  No GPU needed. */
 int swdrv_write_pssm_ascii(const char* path, const int8_t* pssm, int32_t qlen, const char* consensus);
 
+/* Search statistics (an extension; DESIGN.md §12, include/cudasw4_amd_stats.h): Z-scores and E-values by the regression of
+ * FASTA / SSEARCH (Pearson 1998), fitted per query on the scan's own scores.
+ *
+ * The table: hist (uint32, 64 x 256, row-major) counts the subjects by (length bin, min(score, 255)); sumlen (uint64, 64)
+ * sums the true lengths per length bin; subjects with a negative score are in neither.  Length bins are half octaves:
+ * swdrv_length_bin.  Tables add: the table of several shards, ranks or GPUs is the sum of theirs.
+ *
+ * The fit (double precision, sums in ascending (bin, score) order): a bin with row sum n_b > 0 has x_b = ln(sumlen_b / n_b);
+ * N = all cells summed; the cells (b, s) with n_b > 0 and 1 <= s <= 254 are eligible (0: no alignment; 255: censored).
+ * Starting from all eligible cells, at most 10 times: over the included cells, weighted by their counts, n, the sums of x, s,
+ * x^2, x s; b1 = (n Sxs - Sx Ss) / (n Sxx - Sx^2), or 0 when that denominator is 0 or fewer than two bins are included;
+ * a = (Ss - b1 Sx) / n; var = sum w (s - a - b1 x_b)^2 / (n - 2); sd = sqrt(var); the next set is the eligible cells with
+ * |s - a - b1 x_b| / sd <= 5; stop when the set repeats.  n < 100 or var <= 0 at any point: SWDRV_STATS_NO_FIT.
+ *
+ * Per hit of score S and true length L: z = (S - a - b1 ln L) / sd, P = 1 - exp(-exp(-(pi / sqrt 6) z - 0.5772156649015329)),
+ * E = N P.  Under SWDRV_STATS_NO_FIT every z is 0 and every E is -1. */
+#define SWDRV_STATS_OK 0
+#define SWDRV_STATS_NO_FIT 1   /* (SW_STATS_NO_FIT of DESIGN.md §12) */
+typedef struct swdrv_stats {
+    double a, b1, sd;      /* expected score of an unrelated subject of length L: a + b1 ln L; sd of the residuals */
+    int64_t n_included;    /* subjects the last regression ran over */
+    int64_t N;             /* subjects scored: every cell of the table */
+    int32_t rounds;        /* regressions computed */
+    int32_t status;        /* SWDRV_STATS_* */
+} swdrv_stats;
+
+/* on != 0: every query submitted from now on also leaves its table (one launch of sw_score_histogram per GPU on the final
+ * scores, right before the top-K).  Off (the default) nothing is allocated, launched or copied.  Not with queries in flight. */
+int swdrv_set_statistics(swdrv* d, int on);
+/* fit and table of the query collected last (out, hist — 64 x 256 — and sumlen — 64 — may each be NULL); an error when that
+ * query was scanned with the statistics off.  A driver made with swdrv_set_shard sees its shard's table only. */
+int swdrv_last_statistics(swdrv* d, swdrv_stats* out, uint32_t* hist, uint64_t* sumlen);
+/* the fit alone (no GPU needed) */
+int swdrv_stats_from_histogram(const uint32_t* hist, const uint64_t* sumlen, swdrv_stats* out);
+/* z[i] and e[i] (each may be NULL) of n hits (no GPU needed); lengths below 1 count as 1 */
+int swdrv_evalues(const swdrv_stats* stats, const int32_t* scores, const int32_t* lengths, int n, double* z, double* e);
+/* half-octave length bin: L >= 2: 2 e + ((L >> (e - 1)) & 1) with e = floor(log2 L); L <= 1: 0 */
+int swdrv_length_bin(int32_t length);
+
 /* ---- input helpers (no GPU needed): what `align` does to its inputs before the scan ---- */
 
 /* ConvertAA_20 (convert.cuh:6-34): letters -> codes 0..20 */
