@@ -38,6 +38,9 @@ PSSM_EXPORTS = ["sw_set_query_pssm", "sw_query_is_pssm", "sw_align_hits_pssm", "
 # ... and include/cudasw4_amd_stats.h (search statistics: the (length bin, score) histogram of a scan's scores)
 STATS_EXPORTS = ["sw_score_histogram"]
 STATS_LBINS, STATS_SBINS = 64, 256
+# ... and include/cudasw4_amd_rank.h (ranking by E-value: Z-score keys for sw_topk, and the gather behind it)
+RANK_EXPORTS = ["sw_zscore_keys", "sw_gather_hits"]
+RANK_KEY_NONE = -3.0e38   # as float32: the key of a subject that was not scored
 
 
 # sw_align_hits (include/cudasw4_amd.h): result records, statuses, flags, CIGAR op codes
@@ -138,6 +141,10 @@ def _load():
         L.sw_query_is_pssm.argtypes = [vp]
     if hasattr(L, "sw_score_histogram"):
         L.sw_score_histogram.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
+    if hasattr(L, "sw_zscore_keys"):
+        dbl = ctypes.c_double
+        L.sw_zscore_keys.argtypes = [vp, vp, vp, i64, dbl, dbl, dbl, dbl, vp, vp, vp, vp]
+        L.sw_gather_hits.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, vp, vp]
     return L
 
 
@@ -345,6 +352,26 @@ def score_histogram(ctx, scores, lengths, n, hist, sumlen, skipped, stream=0):
         raise SwError(-1, "this build of libcudasw4_amd.so has no sw_score_histogram")
     check(lib.sw_score_histogram(ctx.handle if ctx is not None else None, scores or None, lengths or None, n, hist or None,
                                  sumlen or None, skipped or None, stream or None))
+
+
+def zscore_keys(ctx, scores, lengths, n, a, b1, sd, z_min, keys, positions=0, count=0, stream=0):
+    """sw_zscore_keys (include/cudasw4_amd_rank.h): keys[i] = float32 of the Z-score (scores[i] - a - b1 ln max(lengths[i], 1)) / sd
+    for scores[i] >= 0, RANK_KEY_NONE otherwise; positions[i] = i when positions is given; *count (uint64) is INCREASED by the
+    subjects with scores[i] >= 0 and z >= z_min (no threshold: -sys.float_info.max).  Every buffer is a device pointer as an
+    integer; the caller zeroes count.  Asynchronous on `stream`."""
+    if not hasattr(lib, "sw_zscore_keys"):
+        raise SwError(-1, "this build of libcudasw4_amd.so has no sw_zscore_keys")
+    check(lib.sw_zscore_keys(ctx.handle if ctx is not None else None, scores or None, lengths or None, n, a, b1, sd, z_min,
+                             keys or None, positions or None, count or None, stream or None))
+
+
+def gather_hits(ctx, positions, k, scores, ids, out_scores, out_ids, stream=0):
+    """sw_gather_hits (include/cudasw4_amd_rank.h): out_scores[j], out_ids[j] = scores[p], ids[p] for p = positions[j], the k
+    positions a sw_topk over keys chose; p = -1 gives (-1, -1).  Device pointers as integers; asynchronous on `stream`."""
+    if not hasattr(lib, "sw_gather_hits"):
+        raise SwError(-1, "this build of libcudasw4_amd.so has no sw_gather_hits")
+    check(lib.sw_gather_hits(ctx.handle if ctx is not None else None, positions or None, k, scores or None, ids or None,
+                             out_scores or None, out_ids or None, stream or None))
 
 
 def topk_temp_bytes(n, k):

@@ -23,6 +23,7 @@
 #include "pssm_build.hpp"
 #include "pssm_query.hpp"
 #include "search_driver.hpp"
+#include "search_rank.hpp"
 #include "search_stats.hpp"
 #include "sequence_reader.hpp"
 
@@ -154,6 +155,16 @@ const EvalueReport* evalueReport(const ProgramOptions& o, const ScanResult& r, E
     return o.reportEvalues() ? &storage : nullptr;
 }
 
+// --rankBy evalue --maxEvalue X --verbose: how many subjects of the whole DB lie at or under the threshold, and how many of
+// them the --top list reports
+void reportSignificant(const ProgramOptions& o, const ScanResult& r, const SearchDriver& d, const EvalueReport* ev) {
+    if (!o.verbose || !o.rankByEvalue() || !o.haveMaxEvalue || !(o.maxEvalue > 0) || !ev) return;
+    if (r.significant < 0) { std::cout << "significant: no fit\n"; return; }
+    size_t reported = 0;
+    for (size_t i = 0; i < r.scores.size(); i++) reported += ev->shows(ev->of(r, d, i)) ? 1 : 0;
+    std::cout << "significant: " << r.significant << " subjects at E <= " << o.maxEvalue << " (" << reported << " reported)\n";
+}
+
 // --iterations / --outPssm: the rounds of one query behind its first scan (pssm_build.hpp; DESIGN.md "Building a PSSM").
 struct IterationResult {
     std::vector<int8_t> built;              // the PSSM built from the last round's results
@@ -230,6 +241,7 @@ void processQueryFile(const std::string& file, const ProgramOptions& o, SearchDr
     // how many queries may be pending once a query of this length has been submitted
     auto max_in_flight = [&](size_t queryLength) {
         if (iteration) return 1;   // the rounds of a query are scans of their own: nothing else may be in flight
+        if (o.rankByEvalue()) return 1;   // the second half of a ranked query reads its score array again (SearchDriver::setRanking)
         if (pipe) return pipe[0] == '1' ? 2 : 1;
         return driver.preferredInFlight(int32_t(std::min<size_t>(queryLength, size_t(INT32_MAX))));
     };
@@ -258,6 +270,7 @@ void processQueryFile(const std::string& file, const ProgramOptions& o, SearchDr
                 printScanResultTSV(out, r, driver, interactive ? -1 : q.num, int64_t(q.sequence.size()), interactive ? "-" : q.header, al, ev);
             }
             out.flush();
+            reportSignificant(o, r, driver, ev);
         }
     };
     try {
@@ -306,6 +319,7 @@ void processPssmQuery(const PssmQuery& q, const ProgramOptions& o, SearchDriver&
             printScanResultTSV(out, r, driver, 0, int64_t(q.length()), q.name, al, ev);
         }
         out.flush();
+        reportSignificant(o, r, driver, ev);
     }
     const BenchmarkStats total = driver.totalTimerStop();
     if (o.verbose) std::cout << "Total time: " << total.seconds << " s, " << total.gcups << " GCUPS\n";
@@ -333,9 +347,11 @@ int main(int argc, char** argv) {
         if (options.buildsPssm() && !options.haveInclusionScore && !options.haveInclusionEvalue)
             throw std::runtime_error("--iterations above 1 and --outPssm need --inclusionScore S (results go into the PSSM by raw score, "
                                      "at least S) or --inclusionEvalue X (by their E-values, at most X)");
+        if (options.rankBy != "score" && options.rankBy != "evalue")
+            throw std::runtime_error("--rankBy must be score or evalue, not '" + options.rankBy + "'");
         if (options.haveMaxEvalue && !(options.maxEvalue >= 0)) throw std::runtime_error("--maxEvalue must not be negative");
         if (options.haveInclusionEvalue && !(options.inclusionEvalue >= 0)) throw std::runtime_error("--inclusionEvalue must not be negative");
-        if (options.wantStatistics() && options.interactive) throw std::runtime_error("--evalues / --maxEvalue / --inclusionEvalue cannot be combined with --interactive");
+        if (options.wantStatistics() && options.interactive) throw std::runtime_error("--evalues / --maxEvalue / --inclusionEvalue / --rankBy evalue cannot be combined with --interactive");
         if (!(options.pseudocount > 0)) throw std::runtime_error("--pseudocount must be positive");
         if (options.buildsPssm() && options.interactive) throw std::runtime_error("--iterations / --outPssm cannot be combined with --interactive");
         if (options.buildsPssm() && options.numTopOutputs < 1) throw std::runtime_error("--iterations / --outPssm need --top of at least 1: the PSSM is built from the reported results");
@@ -386,6 +402,7 @@ int main(int argc, char** argv) {
         }
         if (options.loadFullDBToGpu) driver.prefetchDBToGpus();
         if (options.wantStatistics()) enable_statistics(driver, true);
+        if (options.rankByEvalue()) set_ranking(driver, true, options.haveMaxEvalue ? options.maxEvalue : 0.0);
         std::unique_ptr<HitAligner> aligner;
         if (options.reportAlignments() || options.buildsPssm()) aligner = std::make_unique<HitAligner>(driver);
         std::unique_ptr<PssmBuilder> iteration;   // (non-null: every query goes through its rounds)

@@ -40,6 +40,7 @@ void printOptions(const ProgramOptions& o) {
     if (o.pseudocount != 10.0) std::cout << "pseudocount: " << o.pseudocount << "\n";
     if (o.reportEvalues()) std::cout << "evalues: 1\n";
     if (o.haveMaxEvalue) std::cout << "maxEvalue: " << o.maxEvalue << "\n";
+    if (o.haveRankBy) std::cout << "rankBy: " << o.rankBy << "\n";
     if (!o.outPssm.empty()) std::cout << "outPssm: " << o.outPssm << "\n";
     std::cout << "blosum: " << substitution_matrix(o.matrix).name << "\n";
     std::cout << "singlePassType: " << to_string(o.kernels.singlePassType) << "\n";
@@ -84,6 +85,7 @@ bool parseArgs(int argc, char** argv, ProgramOptions& o) {
         else if (arg == "--inclusionEvalue") { o.inclusionEvalue = std::atof(value(i).c_str()); o.haveInclusionEvalue = true; }
         else if (arg == "--evalues") o.evalues = true;
         else if (arg == "--maxEvalue") { o.maxEvalue = std::atof(value(i).c_str()); o.haveMaxEvalue = true; }
+        else if (arg == "--rankBy") { o.rankBy = value(i); o.haveRankBy = true; }
         else if (arg == "--pseudocount") o.pseudocount = std::atof(value(i).c_str());
         else if (arg == "--outPssm") o.outPssm = value(i);
         else if (arg == "--printLengthPartitions") o.printLengthPartitions = true;
@@ -163,7 +165,11 @@ void printHelp(char** argv) {
     std::cout << "      --evalues : Report a Z-score and an E-value with every result: the scores of the whole scan are regressed on the\n"
                  "        logarithm of the subject length (as FASTA / SSEARCH do), fitted per query on the GPU's score histogram. Two more TSV\n"
                  "        columns behind all others; '*' where the scan allows no fit (fewer than 100 usable scores, or no spread).\n";
-    std::cout << "      --maxEvalue X : Implies --evalues. Print only the results of the --top list with an E-value of at most X.\n\n";
+    std::cout << "      --maxEvalue X : Implies --evalues. Print only the results of the --top list with an E-value of at most X.\n";
+    std::cout << "      --rankBy score|evalue : What the --top list is ranked by. Default: score. evalue implies --evalues: the list holds the\n"
+                 "        results of smallest E-value (largest Z-score) of the whole DB, not the best raw scores, which favour long subjects;\n"
+                 "        queries are scanned one at a time. With --maxEvalue X and --verbose, also the number of subjects of the DB with an\n"
+                 "        E-value of at most X. The raw-score list where the scan allows no fit.\n\n";
     std::cout << "   Memory\n";
     std::cout << "      --maxGpuMem val : Try not to use more than val bytes of gpu memory per gpu. Uses all available gpu memory by default\n";
     std::cout << "      --maxTempBytes val : Size of temp storage in GPU memory. Can use suffix K,M,G. Default val = " << d.memory.maxTempBytes << "\n";

@@ -42,7 +42,12 @@ struct ProgramOptions {
     double maxEvalue = 0;
     bool haveInclusionEvalue = false;
     double inclusionEvalue = 0;
-    bool reportEvalues() const { return evalues || haveMaxEvalue; }
+    // --rankBy score|evalue (search_rank.hpp; an extension): evalue ranks the --top list by E-value instead of raw score,
+    // implies --evalues and scans one query at a time; the value is checked in main, before any device is opened
+    bool haveRankBy = false;
+    std::string rankBy = "score";
+    bool rankByEvalue() const { return rankBy == "evalue"; }
+    bool reportEvalues() const { return evalues || haveMaxEvalue || rankByEvalue(); }
     bool wantStatistics() const { return reportEvalues() || haveInclusionEvalue; }
     bool prefetchDBFile = false;
     int numTopOutputs = 10;

@@ -135,6 +135,8 @@ int swdrv_scan(swdrv* d, const char* query, int32_t qlen, int32_t* scores, int64
         if (num_overflows) *num_overflows = r.stats.numOverflows;
         d->lastRescored = r.stats.numRescored;
         d->lastTable = std::move(r.table);
+        d->lastSignificant = r.significant;
+        d->lastZMin = r.zMin;
         if (seconds) *seconds = r.stats.seconds;
         if (gcups) *gcups = r.stats.gcups;
     });
@@ -157,6 +159,8 @@ int swdrv_scan_collect(swdrv* d, int32_t* scores, int64_t* ids, int cap, int* nr
         if (num_overflows) *num_overflows = r.stats.numOverflows;
         d->lastRescored = r.stats.numRescored;
         d->lastTable = std::move(r.table);
+        d->lastSignificant = r.significant;
+        d->lastZMin = r.zMin;
         if (seconds) *seconds = r.stats.seconds;
         if (gcups) *gcups = r.stats.gcups;
     });

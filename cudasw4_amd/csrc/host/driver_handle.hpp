@@ -12,6 +12,8 @@ struct swdrv {
     std::shared_ptr<swh::Database> db;
     int lastRescored = 0;
     std::vector<swh::ScoreTable> lastTable;   // ScanResult::table of the query collected last (search_stats.cpp)
+    int64_t lastSignificant = -1;             // ScanResult::significant and ::zMin of that query (search_rank.cpp)
+    double lastZMin = 0;
 };
 
 namespace swh {

@@ -8,6 +8,7 @@
 #include <time.h>
 
 #include <cctype>
+#include <cfloat>
 #include <cmath>
 
 #include <algorithm>
@@ -343,6 +344,19 @@ struct SearchDriver::Gpu {
         bool tapped = false;
     };
     ResultSlot res[SearchDriver::kMaxInFlight];
+    // E-value ranking (SearchDriver::setRanking): keys and identity positions of the shard, the top-K's choice among them
+    // and the threshold count; one set per GPU (one query in flight), allocated with the first ranked query
+    struct Rank {
+        float* d_keys = nullptr;
+        int32_t* d_pos = nullptr;
+        size_t cap = 0;
+        float* d_topKey = nullptr;
+        int32_t* d_topPos = nullptr;
+        int topCap = 0;
+        unsigned long long* d_count = nullptr;
+        unsigned long long* h_count = nullptr;
+        bool counted = false;   // the query finished last left its count in h_count
+    } rank;
     int lastTop = 0;
     const float* lastTopS = nullptr;   // the finished slot's lists (valid until that slot is reused)
     const int32_t* lastTopI = nullptr;
@@ -499,6 +513,8 @@ SearchDriver::~SearchDriver() {
             (void)hipHostFree(r.h_topS); (void)hipHostFree(r.h_topI); (void)hipHostFree(r.h_ovf);
             (void)hipFree(r.d_table); (void)hipHostFree(r.h_table);
         }
+        (void)hipFree(g.rank.d_keys); (void)hipFree(g.rank.d_pos); (void)hipFree(g.rank.d_topKey); (void)hipFree(g.rank.d_topPos);
+        (void)hipFree(g.rank.d_count); (void)hipHostFree(g.rank.h_count);
         for (auto* v : {&g.timed, &g.freeTimed})
             for (TimedLaunch& t : *v) { (void)hipEventDestroy(t.ev0); (void)hipEventDestroy(t.ev1); }
         (void)hipFree(g.d_scores); (void)hipFree(g.d_ids); (void)hipFree(g.d_ovfPos); (void)hipFree(g.d_ovfCount);
@@ -1166,6 +1182,103 @@ bool SearchDriver::prepareLane(Gpu& g, int32_t queryLength) {
     return true;
 }
 
+// room for a top-kk of the shard: the lane's device lists and scratch, the result slot's pinned lists
+template <class GpuT, class SlotT>
+static void ensure_topk_buffers(GpuT& g, SlotT& rs, int kk) {
+    if (kk > g.topCapacity) {
+        (void)hipFree(g.d_topS); (void)hipFree(g.d_topI);
+        g.d_topS = nullptr; g.d_topI = nullptr; g.topCapacity = 0;
+        HIPCHECK(hipMalloc(&g.d_topS, kk * sizeof(float)));
+        HIPCHECK(hipMalloc(&g.d_topI, kk * sizeof(int32_t)));
+        g.topCapacity = kk;
+    }
+    if (kk > rs.topCap) {
+        (void)hipHostFree(rs.h_topS); (void)hipHostFree(rs.h_topI);
+        rs.h_topS = nullptr; rs.h_topI = nullptr; rs.topCap = 0;
+        HIPCHECK(hipHostMalloc(&rs.h_topS, kk * sizeof(float)));
+        HIPCHECK(hipHostMalloc(&rs.h_topI, kk * sizeof(int32_t)));
+        rs.topCap = kk;
+    }
+    const size_t tb = sw_topk_temp_bytes(int64_t(g.numLocal), kk);
+    if (tb > g.topkTempBytes) {
+        (void)hipFree(g.d_topkTemp);
+        g.d_topkTemp = nullptr;
+        g.topkTempBytes = 0;
+        HIPCHECK(hipMalloc(&g.d_topkTemp, tb));
+        g.topkTempBytes = tb;
+    }
+}
+
+// the copies of the lane's device lists into the result slot's pinned ones
+template <class GpuT, class SlotT>
+static void copy_topk_lists(GpuT& g, SlotT& rs, int kk) {
+    HIPCHECK(hipMemcpyAsync(rs.h_topS, g.d_topS, kk * sizeof(float), hipMemcpyDeviceToHost, g.stream));
+    HIPCHECK(hipMemcpyAsync(rs.h_topI, g.d_topI, kk * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
+    rs.top = kk;
+}
+
+// the top-kk by raw score of the lane's score array, on its work stream
+template <class GpuT, class SlotT>
+static void enqueue_score_topk(GpuT& g, SlotT& rs, int kk) {
+    if (kk <= 0) return;
+    ensure_topk_buffers(g, rs, kk);
+    {
+        TraceRange traceTop("top-%d of %ld scores", kk, long(g.numLocal));
+        SWCHECK(sw_topk(g.ctx, g.d_scores, g.d_ids, int64_t(g.numLocal), kk, g.d_topS, g.d_topI, g.d_topkTemp,
+                        g.topkTempBytes, g.stream));
+    }
+    copy_topk_lists(g, rs, kk);
+}
+
+// The second half of a query under E-value ranking (setRanking), enqueued by collect() once the tables of all GPUs are
+// fitted: Z-score keys of the lane's score array with identity positions, the top-K over the keys, the gather of the raw
+// scores and ids behind the chosen positions, and the copies.  No fit: the raw-score top-K a scan enqueues otherwise.
+void SearchDriver::enqueueRankedOnGpu(Gpu& g, int slot, int k, const RankFit& fit, double zMin) {
+    Gpu::ResultSlot& rs = g.res[slot];
+    g.use();
+    Gpu::LaneGuard laneGuard(g, rs.lane);
+    Gpu::Rank& r = g.rank;
+    r.counted = false;
+    const int kk = int(std::min<size_t>(size_t(std::max(k, 0)), g.numLocal));
+    if (!fit.ok) {
+        enqueue_score_topk(g, rs, kk);
+    } else {
+        const size_t n = g.numLocal;
+        if (n > r.cap) {
+            (void)hipFree(r.d_keys); (void)hipFree(r.d_pos);
+            r.d_keys = nullptr; r.d_pos = nullptr; r.cap = 0;
+            HIPCHECK(hipMalloc(&r.d_keys, n * sizeof(float)));
+            HIPCHECK(hipMalloc(&r.d_pos, n * sizeof(int32_t)));
+            r.cap = n;
+        }
+        if (!r.d_count) HIPCHECK(hipMalloc(&r.d_count, sizeof(unsigned long long)));
+        if (!r.h_count) HIPCHECK(hipHostMalloc(&r.h_count, sizeof(unsigned long long)));
+        if (kk > r.topCap) {
+            (void)hipFree(r.d_topKey); (void)hipFree(r.d_topPos);
+            r.d_topKey = nullptr; r.d_topPos = nullptr; r.topCap = 0;
+            HIPCHECK(hipMalloc(&r.d_topKey, kk * sizeof(float)));
+            HIPCHECK(hipMalloc(&r.d_topPos, kk * sizeof(int32_t)));
+            r.topCap = kk;
+        }
+        HIPCHECK(hipMemsetAsync(r.d_count, 0, sizeof(unsigned long long), g.stream));
+        if (rankHooks_->keys(g.ctx, g.d_scores, g.d_lengths, int64_t(n), fit.a, fit.b1, fit.sd, zMin, r.d_keys, r.d_pos, r.d_count, g.stream) != 0)
+            throw std::runtime_error(std::string("Z-score keys: ") + sw_last_error());
+        HIPCHECK(hipMemcpyAsync(r.h_count, r.d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, g.stream));
+        r.counted = true;
+        if (kk > 0) {
+            ensure_topk_buffers(g, rs, kk);
+            {
+                TraceRange traceTop("top-%d of %ld Z-score keys", kk, long(n));
+                SWCHECK(sw_topk(g.ctx, r.d_keys, r.d_pos, int64_t(n), kk, r.d_topKey, r.d_topPos, g.d_topkTemp, g.topkTempBytes, g.stream));
+            }
+            if (rankHooks_->gather(g.ctx, r.d_topPos, kk, g.d_scores, g.d_ids, g.d_topS, g.d_topI, g.stream) != 0)
+                throw std::runtime_error(std::string("gather of the ranked hits: ") + sw_last_error());
+            copy_topk_lists(g, rs, kk);
+        }
+    }
+    HIPCHECK(hipEventRecord(rs.done, g.stream));
+}
+
 void SearchDriver::enqueueOnGpu(Gpu& g, int32_t queryLength, int k, int slot, bool inFlight) {
     Gpu::ResultSlot& rs = g.res[slot];
     rs.used = false;
@@ -1228,39 +1341,8 @@ void SearchDriver::enqueueOnGpu(Gpu& g, int32_t queryLength, int k, int slot, bo
             HIPCHECK(hipMemcpyAsync(rs.h_table, rs.d_table, sizeof(ScoreTable), hipMemcpyDeviceToHost, g.stream));
             rs.tapped = true;
         }
-        const int kk = int(std::min<size_t>(size_t(std::max(k, 0)), g.numLocal));
-        if (kk > 0) {
-            if (kk > g.topCapacity) {
-                (void)hipFree(g.d_topS); (void)hipFree(g.d_topI);
-                g.d_topS = nullptr; g.d_topI = nullptr; g.topCapacity = 0;
-                HIPCHECK(hipMalloc(&g.d_topS, kk * sizeof(float)));
-                HIPCHECK(hipMalloc(&g.d_topI, kk * sizeof(int32_t)));
-                g.topCapacity = kk;
-            }
-            if (kk > rs.topCap) {
-                (void)hipHostFree(rs.h_topS); (void)hipHostFree(rs.h_topI);
-                rs.h_topS = nullptr; rs.h_topI = nullptr; rs.topCap = 0;
-                HIPCHECK(hipHostMalloc(&rs.h_topS, kk * sizeof(float)));
-                HIPCHECK(hipHostMalloc(&rs.h_topI, kk * sizeof(int32_t)));
-                rs.topCap = kk;
-            }
-            const size_t tb = sw_topk_temp_bytes(int64_t(g.numLocal), kk);
-            if (tb > g.topkTempBytes) {
-                (void)hipFree(g.d_topkTemp);
-                g.d_topkTemp = nullptr;
-                g.topkTempBytes = 0;
-                HIPCHECK(hipMalloc(&g.d_topkTemp, tb));
-                g.topkTempBytes = tb;
-            }
-            {
-                TraceRange traceTop("top-%d of %ld scores", kk, long(g.numLocal));
-                SWCHECK(sw_topk(g.ctx, g.d_scores, g.d_ids, int64_t(g.numLocal), kk, g.d_topS, g.d_topI, g.d_topkTemp,
-                                g.topkTempBytes, g.stream));
-            }
-            HIPCHECK(hipMemcpyAsync(rs.h_topS, g.d_topS, kk * sizeof(float), hipMemcpyDeviceToHost, g.stream));
-            HIPCHECK(hipMemcpyAsync(rs.h_topI, g.d_topI, kk * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
-            rs.top = kk;
-        }
+        // (under E-value ranking k is 0 here: the top-K needs the fit, and collect() enqueues it)
+        enqueue_score_topk(g, rs, int(std::min<size_t>(size_t(std::max(k, 0)), g.numLocal)));
         // per-query totals (addKernel, cudasw4.cuh:46-49,2175): summed on the host after the copy
         HIPCHECK(hipMemcpyAsync(rs.h_ovf, g.d_ovfCount, (ncounters + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
         HIPCHECK(hipEventRecord(rs.done, g.stream));
@@ -1413,6 +1495,15 @@ void SearchDriver::setScoreTap(ScoreTapFn tap) {
     scoreTap_ = tap;
 }
 
+void SearchDriver::setRanking(const RankHooks* hooks, double maxEvalue) {
+    if (pendingCount_) throw std::runtime_error("setRanking with queries in flight: collect() them first");
+    if (hooks && !(hooks->keys && hooks->gather && hooks->fit && hooks->zForEvalue && hooks->order))
+        throw std::runtime_error("setRanking: incomplete hooks");
+    if (hooks && !scoreTap_) throw std::runtime_error("setRanking: E-value ranking needs the score tap (setScoreTap first)");
+    rankHooks_ = hooks;
+    rankMaxEvalue_ = hooks && maxEvalue > 0 ? maxEvalue : 0;
+}
+
 void SearchDriver::submit(const char* query, int32_t queryLength) {
     check_submit(db_.get(), queryLength, pendingCount_);
     encodedQuery_.resize(size_t(queryLength));
@@ -1432,8 +1523,12 @@ void SearchDriver::submitEncoded(int32_t queryLength) {
     ps.k = numTop_;
     ps.t0 = now_seconds();
     ps.tapped = scoreTap_ != nullptr;
+    ps.ranked = rankHooks_ != nullptr && ps.tapped;
+    // the lane's score array is read again by collect(): nothing may overwrite it, and two lanes' queries would share Gpu::rank
+    if (ps.ranked && pendingCount_ > 0)
+        throw std::runtime_error("E-value ranking allows one query in flight: collect() the pending query before the next submit()");
     if (pendingCount_ == 0) scanT0_ = ps.t0;
-    const int slot = ps.slot, k = ps.k;
+    const int slot = ps.slot, k = ps.ranked ? 0 : ps.k;
     const bool inFlight = pendingCount_ > 0;
     forEachGpu([this, queryLength, k, slot, inFlight](Gpu& g) { enqueueOnGpu(g, queryLength, k, slot, inFlight); });
     nextSlot_ = (nextSlot_ + 1) % kMaxInFlight;
@@ -1454,18 +1549,6 @@ ScanResult SearchDriver::collect() {
     if (first) std::rethrow_exception(first);
 
     ScanResult result;
-    struct Hit { int score; int64_t id; };
-    std::vector<Hit> hits;
-    for (auto& gp : gpus_) {
-        Gpu& g = *gp;
-        result.stats.numOverflows += g.lastOverflows;
-        result.stats.numRescored += g.lastRescored;
-        for (int i = 0; i < g.lastTop; i++) hits.push_back(Hit{int(g.lastTopS[i]), idBase_ + g.toGlobal(g.lastTopI[i])});
-    }
-    // host merge of the per-GPU lists (replaces cudasw4.cuh:1415-1463): score desc, id asc
-    std::sort(hits.begin(), hits.end(), [](const Hit& a, const Hit& b) { return a.score != b.score ? a.score > b.score : a.id < b.id; });
-    if (int(hits.size()) > ps.k) hits.resize(size_t(std::max(ps.k, 0)));
-    for (const Hit& h : hits) { result.scores.push_back(h.score); result.referenceIds.push_back(h.id); }
     if (ps.tapped) {   // integer tables: the sum over the GPUs is the table of the whole DB, in any order
         result.table.emplace_back();
         ScoreTable& sum = result.table.back();
@@ -1478,6 +1561,66 @@ ScanResult SearchDriver::collect() {
             sum.skipped += t->skipped;
         }
     }
+    // E-value ranking: the fit of the whole DB's table, then each GPU's candidates by Z-score key (setRanking)
+    RankFit fit;
+    if (ps.ranked) {
+        fit = rankHooks_->fit(result.table.front());
+        const bool threshold = fit.ok && rankMaxEvalue_ > 0;
+        double zMin = -DBL_MAX;
+        if (threshold) {
+            result.zMin = rankHooks_->zForEvalue(fit.N, rankMaxEvalue_);
+            zMin = std::max(result.zMin, -DBL_MAX);   // (-infinity: every scored subject)
+        }
+        for (auto& gp : gpus_) {   // (a GPU with a table took part in the scan)
+            try { if (gp->lastTable) enqueueRankedOnGpu(*gp, ps.slot, ps.k, fit, zMin); } catch (...) { if (!first) first = std::current_exception(); }
+        }
+        uint64_t count = 0;
+        for (auto& gp : gpus_) {
+            Gpu& g = *gp;
+            if (!g.lastTable) continue;
+            try {
+                g.use();
+                waitForScan(g, g.res[ps.slot].done, ps.qlen);
+                // (the slot's pinned lists may have been allocated by enqueueRankedOnGpu only: finishOnGpu saw the old pointers)
+                g.lastTop = g.res[ps.slot].top;
+                g.lastTopS = g.res[ps.slot].h_topS;
+                g.lastTopI = g.res[ps.slot].h_topI;
+                if (g.rank.counted) count += *g.rank.h_count;
+                g.spanEnd = now_seconds() - scanT0_;
+            } catch (...) { if (!first) first = std::current_exception(); }
+        }
+        if (first) std::rethrow_exception(first);
+        if (threshold) result.significant = int64_t(count);
+    }
+    struct Hit { int score; int64_t id; };
+    std::vector<Hit> hits;
+    for (auto& gp : gpus_) {
+        Gpu& g = *gp;
+        result.stats.numOverflows += g.lastOverflows;
+        result.stats.numRescored += g.lastRescored;
+        for (int i = 0; i < g.lastTop; i++) hits.push_back(Hit{int(g.lastTopS[i]), idBase_ + g.toGlobal(g.lastTopI[i])});
+    }
+    if (ps.ranked && fit.ok) {
+        // host merge of the per-GPU candidates in double precision: Z-score desc, id asc
+        const size_t nh = hits.size();
+        const int n = int(nh);
+        std::vector<int32_t> scores(nh), lengths(nh), order(nh);
+        std::vector<int64_t> ids(nh);
+        for (int i = 0; i < n; i++) {
+            scores[size_t(i)] = hits[size_t(i)].score;
+            ids[size_t(i)] = hits[size_t(i)].id;
+            lengths[size_t(i)] = db_->length(size_t(hits[size_t(i)].id - idBase_));
+        }
+        rankHooks_->order(fit, scores.data(), lengths.data(), ids.data(), n, order.data());
+        std::vector<Hit> ranked;
+        for (int i = 0; i < n && i < ps.k; i++) ranked.push_back(hits[size_t(order[size_t(i)])]);
+        hits.swap(ranked);
+    } else {
+        // host merge of the per-GPU lists (replaces cudasw4.cuh:1415-1463): score desc, id asc
+        std::sort(hits.begin(), hits.end(), [](const Hit& a, const Hit& b) { return a.score != b.score ? a.score > b.score : a.id < b.id; });
+        if (int(hits.size()) > ps.k) hits.resize(size_t(std::max(ps.k, 0)));
+    }
+    for (const Hit& h : hits) { result.scores.push_back(h.score); result.referenceIds.push_back(h.id); }
 
     // a query's time runs from its submission, or from the end of the query before it when it had to queue behind that
     const double t1 = now_seconds();

@@ -69,6 +69,25 @@ struct ScanResult {  // cudasw4.cuh:82-86
     BenchmarkStats stats;
     // with a score tap: the tables of all GPUs summed (one element); empty without
     std::vector<ScoreTable> table;
+    // under E-value ranking (SearchDriver::setRanking): subjects of the whole DB at or under the E-value threshold (-1: no
+    // threshold, or the scan allows no fit) and the Z-score that threshold stands for
+    int64_t significant = -1;
+    double zMin = 0;
+};
+
+// What E-value ranking needs beyond this file: the two kernels of include/cudasw4_amd_rank.h and the host
+// arithmetic of search_stats.cpp / search_rank.cpp.  Like QueryInstallFn and ScoreTapFn the functions live in the caller's
+// translation unit (search_rank.cpp), so this file names no entry point of the kernel library beyond the boundary.
+struct RankFit { bool ok = false; double a = 0, b1 = 0, sd = 0; int64_t N = 0; };
+struct RankHooks {
+    int (*keys)(sw_ctx* ctx, const float* scores, const int32_t* lengths, int64_t n, double a, double b1, double sd, double zMin,
+                float* keys, int32_t* positions, unsigned long long* count, void* stream);
+    int (*gather)(sw_ctx* ctx, const int32_t* positions, int k, const float* scores, const int32_t* ids, float* outScores,
+                  int32_t* outIds, void* stream);
+    RankFit (*fit)(const ScoreTable& table);
+    double (*zForEvalue)(int64_t N, double evalue);   // -infinity: every scored subject passes
+    // out[0 .. n): the indices of the n candidates by Z-score (double precision) descending, then id ascending
+    void (*order)(const RankFit& fit, const int32_t* scores, const int32_t* lengths, const int64_t* ids, int n, int32_t* out);
 };
 
 // One launch of the scan kernel: a run of adjacent length partitions that use the same arithmetic kind.
@@ -215,6 +234,16 @@ public:
     using ScoreTapFn = int (*)(sw_ctx* ctx, const float* scores, const int32_t* lengths, int64_t n, void* deviceOut, void* stream);
     void setScoreTap(ScoreTapFn tap);
     bool hasScoreTap() const { return scoreTap_ != nullptr; }
+    // Ranking by E-value: with hooks set (and a score tap, which the caller sets as well), submit() enqueues
+    // the scan and the tap but no top-K; collect() waits for the tables, fits them, and enqueues on every GPU — on the lane
+    // and stream whose score array the query used — Z-score keys, the top-K over them and the gather of the raw scores and
+    // ids, waits again and orders the GPUs' candidates in double precision.  ScanResult keeps raw scores and global ids, now
+    // in E-value order.  Where the scan allows no fit, collect() enqueues the raw-score top-K instead.  maxEvalue > 0: the
+    // subjects with E <= maxEvalue are counted as well (ScanResult::significant).  The lane's score array must survive until
+    // collect(), so ONE query may be in flight.  nullptr: ranking by raw score — nothing is allocated, launched or copied
+    // beyond what a scan did before.  Not with queries in flight.
+    void setRanking(const RankHooks* hooks, double maxEvalue);
+    bool ranksByEvalue() const { return rankHooks_ != nullptr; }
     ScanResult collect();
     int inFlight() const { return int(pendingCount_); }
 
@@ -288,6 +317,7 @@ private:
     bool prepareLane(Gpu& g, int32_t queryLength);
     bool laneEligible(const Gpu& g, int32_t queryLength) const;
     void finishOnGpu(Gpu& g, int slot, int32_t qlen);
+    void enqueueRankedOnGpu(Gpu& g, int slot, int k, const RankFit& fit, double zMin);
     void waitForScan(Gpu& g, void* doneEvent, int32_t qlen);
     void registerStreamedRanges();
     void unregisterRanges();
@@ -309,10 +339,12 @@ private:
     std::vector<int8_t> encodedQuery_;
     QueryInstallFn queryInstall_ = nullptr;   // submitWith: what installs encodedQuery_ (nullptr: sw_set_query)
     ScoreTapFn scoreTap_ = nullptr;
+    const RankHooks* rankHooks_ = nullptr;
+    double rankMaxEvalue_ = 0;
     double scanT0_ = 0;
     double watchdogSeconds_ = 60.0;   // CUDASW4_AMD_WATCHDOG_SECONDS: base of collect()'s deadline (0: none)
     // queries submitted and not yet collected, oldest first (a ring of kMaxInFlight result slots per GPU)
-    struct PendingScan { int slot = 0; int32_t qlen = 0; int k = 0; double t0 = 0; bool tapped = false; };
+    struct PendingScan { int slot = 0; int32_t qlen = 0; int k = 0; double t0 = 0; bool tapped = false; bool ranked = false; };
     PendingScan pending_[kMaxInFlight];
     size_t pendingHead_ = 0, pendingCount_ = 0;
     int nextSlot_ = 0;

@@ -25,7 +25,8 @@ EXPORTS = ["swdrv_last_error", "swdrv_create", "swdrv_destroy", "swdrv_open_db",
            "swdrv_tail_overlaps", "swdrv_prefers_two_in_flight", "swdrv_pipeline_launches", "swdrv_handshake_active", "swdrv_preferred_in_flight",
            "swdrv_latency_scans", "swdrv_plan_runs_mode", "swdrv_align_hits", "swdrv_scan_pssm", "swdrv_scan_submit_pssm",
            "swdrv_align_hits_pssm", "swdrv_pssm_from_counts", "swdrv_build_pssm", "swdrv_write_pssm_ascii",
-           "swdrv_set_statistics", "swdrv_last_statistics", "swdrv_stats_from_histogram", "swdrv_evalues", "swdrv_length_bin"]
+           "swdrv_set_statistics", "swdrv_last_statistics", "swdrv_stats_from_histogram", "swdrv_evalues", "swdrv_length_bin",
+           "swdrv_set_ranking", "swdrv_last_ranking", "swdrv_zscore_for_evalue", "swdrv_rank_order"]
 
 
 class DriverError(RuntimeError):
@@ -200,6 +201,43 @@ def _stats_struct(stats):
                   int(stats["rounds"]), int(stats["status"]))
 
 
+RANK_SCORE, RANK_EVALUE = 0, 1
+
+
+def _rank_fns():
+    """swdrv_set_ranking / swdrv_last_ranking / swdrv_zscore_for_evalue / swdrv_rank_order, bound on first use (like
+    swdrv_align_hits: not in every build of this C ABI)"""
+    setr, last, zfor, order = lib.swdrv_set_ranking, lib.swdrv_last_ranking, lib.swdrv_zscore_for_evalue, lib.swdrv_rank_order
+    if setr.argtypes is None:
+        vp = ctypes.c_void_p
+        setr.argtypes = [vp, ctypes.c_int, ctypes.c_double]
+        last.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)]
+        zfor.argtypes = [ctypes.c_int64, ctypes.c_double]
+        zfor.restype = ctypes.c_double
+        order.argtypes = [ctypes.POINTER(_Stats), vp, vp, vp, ctypes.c_int, vp]
+    return setr, last, zfor, order
+
+
+def zscore_for_evalue(N, evalue):
+    """swdrv_zscore_for_evalue (no GPU needed): the Z-score at which the E-value of a DB of N scored subjects equals `evalue`
+    (-inf for evalue >= N)."""
+    return float(_rank_fns()[2](int(N), float(evalue)))
+
+
+def rank_order(stats, scores, lengths, ids):
+    """swdrv_rank_order (no GPU needed): the indices of the hits by Z-score under `stats` (a fit dict) descending, equal
+    Z-scores by ascending id -> int32 array."""
+    sc = np.ascontiguousarray(scores, dtype=np.int32)
+    ln = np.ascontiguousarray(lengths, dtype=np.int32)
+    ii = np.ascontiguousarray(ids, dtype=np.int64)
+    if not len(sc) == len(ln) == len(ii):
+        raise ValueError("scores, lengths and ids must have one length")
+    out = np.zeros(len(sc), dtype=np.int32)
+    c = _stats_struct(stats)
+    _check(_rank_fns()[3](ctypes.byref(c), sc.ctypes.data, ln.ctypes.data, ii.ctypes.data, len(sc), out.ctypes.data))
+    return out
+
+
 def pssm_from_counts(master_codes, counts, wcounts, matrix=62, pseudocount=10.0, with_raw=False):
     """swdrv_pssm_from_counts (no GPU needed): residue counts (qlen x 20, uint32) and weighted counts (qlen x 20, uint64) of a
     master sequence's aligned hits -> ((qlen, 21) int8 PSSM, lambda), or (PSSM, lambda, raw (qlen, 20) float64 scores)."""
@@ -360,11 +398,42 @@ class Driver:
         self.handle = h
         self.num_top = num_top
         self.statistics = False
+        self.ranking = "score"
+        self.max_evalue = None
+
+    def set_ranking(self, by="score", max_evalue=None):
+        """Ranking of the result lists.  "evalue": statistics on, and every scan from now on returns the num_top
+        subjects of smallest E-value (largest Z-score; ties: ascending id) — "scores" and "ids" stay raw scores and global ids,
+        "zscores" and "evalues" stay aligned with them, so align_hits, build_pssm and iterate take the list as it is.  With
+        max_evalue the dicts also carry "n_significant": the subjects of the whole DB with E <= max_evalue (-1 where the scan
+        allows no fit; the list is then the raw-score list).  One query in flight.  "score": the raw-score lists again (the
+        statistics stay as they are).  Not with queries in flight."""
+        if by not in ("score", "evalue"):
+            raise ValueError("ranking must be 'score' or 'evalue', not %r" % (by,))
+        if by == "score" and max_evalue is not None:
+            raise ValueError("max_evalue belongs to ranking by 'evalue'")
+        x = float(max_evalue) if max_evalue is not None else 0.0
+        if max_evalue is not None and not x > 0:
+            raise ValueError("max_evalue must be positive")
+        _check(_rank_fns()[0](self.handle, RANK_EVALUE if by == "evalue" else RANK_SCORE, x))
+        self.ranking = by
+        self.max_evalue = x if max_evalue is not None else None
+        if by == "evalue":
+            self.statistics = True
+
+    def last_ranking(self):
+        """(count, z_min) of the query collected last (swdrv_last_ranking): the subjects at or under the E-value threshold over
+        all GPUs (-1: no threshold, no fit, or ranked by score) and the Z-score the threshold stands for."""
+        c, z = ctypes.c_int64(), ctypes.c_double()
+        _check(_rank_fns()[1](self.handle, ctypes.byref(c), ctypes.byref(z)))
+        return int(c.value), float(z.value)
 
     def set_statistics(self, on=True):
         """Search statistics: from now on every scan also histograms its scores on the GPU, and the dicts of
         scan / scan_pssm / collect carry "zscores" and "evalues" (float64, aligned with "scores") and "stats" (the fit: a, b1,
         sd, n_included, N, rounds, status; plus the table: hist, sumlen).  Not with queries in flight."""
+        if not on and self.ranking == "evalue":
+            raise ValueError("ranking by E-value needs the statistics: set_ranking('score') first")
         _check(_stats_fns()[0](self.handle, int(bool(on))))
         self.statistics = bool(on)
 
@@ -390,6 +459,8 @@ class Driver:
         c = _stats_struct(st)
         _check(_stats_fns()[3](ctypes.byref(c), sc.ctypes.data, lengths.ctypes.data, len(ids), z.ctypes.data, e.ctypes.data))
         result["zscores"], result["evalues"], result["stats"] = z, e, st
+        if self.ranking == "evalue" and self.max_evalue is not None:
+            result["n_significant"] = self.last_ranking()[0]
         return result
 
     def close(self):

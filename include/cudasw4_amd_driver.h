@@ -265,6 +265,35 @@ int swdrv_evalues(const swdrv_stats* stats, const int32_t* scores, const int32_t
 /* half-octave length bin: L >= 2: 2 e + ((L >> (e - 1)) & 1) with e = floor(log2 L); L <= 1: 0 */
 int swdrv_length_bin(int32_t length);
 
+/* Ranking by E-value (an extension; DESIGN.md §13, include/cudasw4_amd_rank.h).  The list of a scan is the top-K by raw
+ * score; under the statistics above a long subject collects b1 ln L more points than a short one by chance alone, so the
+ * list by E-value — by Z-score, descending — is another one.  SWDRV_RANK_EVALUE switches the statistics on and makes every
+ * query submitted from now on return the num_top subjects of largest Z-score (ties: ascending id): the scan and its table as
+ * before; then, once the table is fitted, on every GPU Z-score keys of all its scores (sw_zscore_keys), sw_topk over the keys
+ * and the gather of the raw scores and ids (sw_gather_hits); the GPUs' candidates are ordered on the host in double precision
+ * (swdrv_rank_order).  Selection on the device runs on float keys: two subjects may change places, or trade the last place,
+ * only when their Z-scores differ by less than 1e-6 max(1, |z|).  Results keep raw scores and global ids, so swdrv_align_hits,
+ * swdrv_build_pssm and swdrv_evalues take them unchanged.  Where the scan allows no fit the list is the raw-score list.
+ * max_evalue > 0: the subjects of the whole DB with score >= 0 and E <= max_evalue are counted as well (swdrv_last_ranking);
+ * <= 0: no threshold.  Under SWDRV_RANK_EVALUE ONE query may be in flight: a second swdrv_scan_submit is an error.
+ * SWDRV_RANK_SCORE (the default): the raw-score list; nothing is allocated, launched or copied beyond what the statistics
+ * setting asks for (it stays as it is).  Not with queries in flight. */
+#define SWDRV_RANK_SCORE 0
+#define SWDRV_RANK_EVALUE 1
+int swdrv_set_ranking(swdrv* d, int mode, double max_evalue);
+/* of the query collected last: *count = subjects at or under the threshold, summed over the GPUs (-1: no threshold, no fit, or
+ * ranked by score); *z_min = the Z-score the threshold stands for (-infinity when max_evalue >= N; 0 when count is -1).
+ * Either pointer may be NULL. */
+int swdrv_last_ranking(swdrv* d, int64_t* count, double* z_min);
+/* The Z-score at which the E-value of a DB of N scored subjects equals X (no GPU needed): for 0 < X < N,
+ * z_min = -(ln(-ln1p(-X / N)) + 0.5772156649015329) sqrt(6) / pi; X >= N: -infinity; X <= 0: +infinity; N <= 0 or NaN: NaN. */
+double swdrv_zscore_for_evalue(int64_t N, double X);
+/* out_order[0 .. n): the indices of n hits by Z-score under `stats` (double precision, as swdrv_evalues computes it)
+ * descending, equal Z-scores by ascending id (no GPU needed): the host merge.  Under SWDRV_STATS_NO_FIT: by raw score
+ * descending, then ascending id. */
+int swdrv_rank_order(const swdrv_stats* stats, const int32_t* scores, const int32_t* lengths, const int64_t* ids, int n,
+                     int32_t* out_order);
+
 /* ---- input helpers (no GPU needed): what `align` does to its inputs before the scan ---- */
 
 /* ConvertAA_20 (convert.cuh:6-34): letters -> codes 0..20 */
