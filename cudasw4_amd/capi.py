@@ -41,10 +41,14 @@ STATS_LBINS, STATS_SBINS = 64, 256
 # ... and include/cudasw4_amd_rank.h (ranking by E-value: Z-score keys for sw_topk, and the gather behind it)
 RANK_EXPORTS = ["sw_zscore_keys", "sw_gather_hits"]
 RANK_KEY_NONE = -3.0e38   # as float32: the key of a subject that was not scored
+# ... and include/cudasw4_amd_hsps.h (hit alignment: up to MAX_HSPS non-overlapping local alignments per hit)
+HSPS_EXPORTS = ["sw_align_hsps", "sw_align_hsps_pssm"]
+MAX_HSPS = 16
 
 
 # sw_align_hits (include/cudasw4_amd.h): result records, statuses, flags, CIGAR op codes
 ALIGN_OK, ALIGN_EMPTY, ALIGN_NO_TRACE, ALIGN_SCORE_MISMATCH, ALIGN_BAD_LENGTH = 0, 1, 2, 3, 4
+ALIGN_NOT_COMPUTED = 5   # sw_align_hsps: behind an alignment that has no traceback
 ALIGN_COORDS_ONLY = 1
 CIGAR_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}
 ALIGN_RESULT_FIELDS = ["score", "status", "q_begin", "q_end", "s_begin", "s_end", "columns", "identities", "mismatches",
@@ -74,6 +78,10 @@ class _AlignArgs(ctypes.Structure):
                 ("temp", ctypes.c_void_p), ("temp_bytes", ctypes.c_size_t),
                 ("temp_bytes_needed", ctypes.POINTER(ctypes.c_size_t)), ("phase_events", ctypes.c_void_p),
                 ("stream", ctypes.c_void_p)]
+
+
+class _HspArgs(ctypes.Structure):
+    _fields_ = [("max_hsps", ctypes.c_int32), ("min_score", ctypes.c_int32)]
 
 
 class SwError(RuntimeError):
@@ -315,6 +323,51 @@ def align_hits_pssm(ctx, pssm, consensus, qlen, n, chars, offsets, lengths, max_
                    cigar_offsets, flags, trace_bytes, temp, temp_bytes, ctypes.pointer(need),
                    ctypes.cast(ev, ctypes.c_void_p) if ev is not None else None, stream)
     check(f(ctx.handle if ctx is not None else None, ctypes.byref(a), pssm or None))
+    return int(need.value)
+
+
+def _align_args(query, qlen, n, chars, offsets, lengths, max_subject_len, gop, gex, results, cigar, cigar_offsets, expected_scores,
+                flags, trace_bytes, temp, temp_bytes, stream, phase_events):
+    """-> (sw_align_args, the size_t it reports the scratch in, what has to stay alive during the call)"""
+    need = ctypes.c_size_t(0)
+    ev = (ctypes.c_void_p * 4)(*phase_events) if phase_events is not None else None
+    a = _AlignArgs(query or None, qlen, n, chars, offsets, lengths, max_subject_len, gop, gex, expected_scores, results, cigar,
+                   cigar_offsets, flags, trace_bytes, temp, temp_bytes, ctypes.pointer(need),
+                   ctypes.cast(ev, ctypes.c_void_p) if ev is not None else None, stream)
+    return a, need, ev
+
+
+def align_hsps(ctx, query, qlen, n, chars, offsets, lengths, max_subject_len, gop, gex, results, cigar=0, cigar_offsets=0,
+               max_hsps=1, min_score=1, expected_scores=0, flags=0, trace_bytes=0, temp=0, temp_bytes=0, stream=0,
+               phase_events=None):
+    """sw_align_hsps (include/cudasw4_amd_hsps.h): align_hits with up to max_hsps non-overlapping alignments per pair.
+    results: n * max_hsps records, cigar_offsets: n * max_hsps + 1 entries, slot (i, k) at i * max_hsps + k; alignments
+    k >= 1 that score less than min_score are not reported.  The other arguments and the return value are align_hits'."""
+    if not hasattr(lib, "sw_align_hsps"):
+        raise SwError(-1, "this build of libcudasw4_amd.so has no sw_align_hsps")
+    f = lib.sw_align_hsps
+    if f.argtypes is None:   # bound on first use (CUDASW4_AMD_LIB may name an older build)
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(_AlignArgs), ctypes.POINTER(_HspArgs)]
+    a, need, _keep = _align_args(query, qlen, n, chars, offsets, lengths, max_subject_len, gop, gex, results, cigar, cigar_offsets,
+                                 expected_scores, flags, trace_bytes, temp, temp_bytes, stream, phase_events)
+    h = _HspArgs(max_hsps, min_score)
+    check(f(ctx.handle if ctx is not None else None, ctypes.byref(a), ctypes.byref(h)))
+    return int(need.value)
+
+
+def align_hsps_pssm(ctx, pssm, consensus, qlen, n, chars, offsets, lengths, max_subject_len, gop, gex, results, cigar=0,
+                    cigar_offsets=0, max_hsps=1, min_score=1, expected_scores=0, flags=0, trace_bytes=0, temp=0, temp_bytes=0,
+                    stream=0, phase_events=None):
+    """sw_align_hsps_pssm: align_hsps with a PSSM as the query (pssm, consensus: as align_hits_pssm)."""
+    if not hasattr(lib, "sw_align_hsps_pssm"):
+        raise SwError(-1, "this build of libcudasw4_amd.so has no sw_align_hsps_pssm")
+    f = lib.sw_align_hsps_pssm
+    if f.argtypes is None:
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(_AlignArgs), ctypes.POINTER(_HspArgs), ctypes.c_void_p]
+    a, need, _keep = _align_args(consensus, qlen, n, chars, offsets, lengths, max_subject_len, gop, gex, results, cigar,
+                                 cigar_offsets, expected_scores, flags, trace_bytes, temp, temp_bytes, stream, phase_events)
+    h = _HspArgs(max_hsps, min_score)
+    check(f(ctx.handle if ctx is not None else None, ctypes.byref(a), ctypes.byref(h), pssm or None))
     return int(need.value)
 
 

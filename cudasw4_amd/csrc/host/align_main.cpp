@@ -67,9 +67,12 @@ struct EvalueReport {
     }
 };
 
+// --maxHsps above 1: the alignments of every result, the first one included (nullptr otherwise)
+typedef HitAligner::HspLists HspLists;
+
 // alignments: nullptr without --alignments / --pssmAlignments, else one per result
 void printScanResultPlain(std::ostream& os, const ScanResult& r, const SearchDriver& d, const std::vector<HitAlignment>* alignments = nullptr,
-                          const EvalueReport* ev = nullptr) {
+                          const EvalueReport* ev = nullptr, const HspLists* hsps = nullptr) {
     for (size_t i = 0; i < r.scores.size(); i++) {
         const int64_t id = r.referenceIds[i];
         HitStatistics hs;
@@ -88,18 +91,33 @@ void printScanResultPlain(std::ostream& os, const ScanResult& r, const SearchDri
                << a.r.columns << ". Identities " << a.r.identities << ". Gap opens " << a.r.gap_opens << ". CIGAR "
                << cigar_string(a.cigar) << "\n";
         }
+        // a further alignment's Z-score and E-value: the query's fit applied to its own (non-maximal) score
+        for (size_t k = 1; hsps && k < (*hsps)[i].size(); k++) {
+            const HitAlignment& a = (*hsps)[i][k];
+            const AlignmentColumns c(a.r);
+            os << "Alignment " << i << "." << k + 1 << ". Score " << a.r.score << ". Query " << c.qb << "-" << c.qe << ". Reference " << c.sb
+               << "-" << c.se << ". Length " << a.r.columns << ". Identities " << a.r.identities << ". Gap opens " << a.r.gap_opens
+               << ". CIGAR " << cigar_string(a.cigar);
+            if (ev) {
+                const HitStatistics h = hit_statistics(ev->stats, a.r.score, d.getReferenceLength(id));
+                os << " Z-score: " << EvalueReport::z_text(ev->stats, h) << " E-value: " << EvalueReport::e_text(ev->stats, h);
+            }
+            os << "\n";
+        }
     }
 }
 
-void printTSVHeader(std::ostream& os, bool alignments, bool evalues) {
+void printTSVHeader(std::ostream& os, bool alignments, bool evalues, bool hsps = false) {
     os << "Query number\tQuery length\tQuery header\tResult number\tResult score\tReference length\tReference header\tReference ID in DB";
     if (alignments) os << "\tQuery begin\tQuery end\tReference begin\tReference end\tAlignment length\tIdentities\tGap opens\tCIGAR";
+    if (hsps) os << "\tHSP";
     if (evalues) os << "\tZ-score\tE-value";
     os << "\n";
 }
 
 void printScanResultTSV(std::ostream& os, const ScanResult& r, const SearchDriver& d, int64_t queryId, int64_t queryLength,
-                        std::string_view queryHeader, const std::vector<HitAlignment>* alignments = nullptr, const EvalueReport* ev = nullptr) {
+                        std::string_view queryHeader, const std::vector<HitAlignment>* alignments = nullptr, const EvalueReport* ev = nullptr,
+                        const HspLists* hsps = nullptr) {
     for (size_t i = 0; i < r.scores.size(); i++) {
         const int64_t id = r.referenceIds[i];
         HitStatistics hs;
@@ -115,8 +133,24 @@ void printScanResultTSV(std::ostream& os, const ScanResult& r, const SearchDrive
             os << '\t' << c.qb << '\t' << c.qe << '\t' << c.sb << '\t' << c.se << '\t' << a.r.columns << '\t' << a.r.identities
                << '\t' << a.r.gap_opens << '\t' << cigar_string(a.cigar);
         }
+        if (hsps) os << '\t' << 1;
         if (ev) os << '\t' << EvalueReport::z_text(ev->stats, hs) << '\t' << EvalueReport::e_text(ev->stats, hs);
         os << "\n";
+        // every further alignment: the result's line again with that alignment's score, coordinates and statistics (the
+        // query's fit applied to its own, non-maximal, score)
+        for (size_t k = 1; hsps && k < (*hsps)[i].size(); k++) {
+            const HitAlignment& a = (*hsps)[i][k];
+            const AlignmentColumns c(a.r);
+            os << queryId << '\t' << queryLength << '\t' << queryHeader << '\t' << i << '\t' << a.r.score << '\t'
+               << d.getReferenceLength(id) << '\t' << d.getReferenceHeader(id) << '\t' << id << '\t' << c.qb << '\t' << c.qe << '\t'
+               << c.sb << '\t' << c.se << '\t' << a.r.columns << '\t' << a.r.identities << '\t' << a.r.gap_opens << '\t'
+               << cigar_string(a.cigar) << '\t' << k + 1;
+            if (ev) {
+                const HitStatistics h = hit_statistics(ev->stats, a.r.score, d.getReferenceLength(id));
+                os << '\t' << EvalueReport::z_text(ev->stats, h) << '\t' << EvalueReport::e_text(ev->stats, h);
+            }
+            os << "\n";
+        }
     }
 }
 
@@ -169,7 +203,21 @@ void reportSignificant(const ProgramOptions& o, const ScanResult& r, const Searc
 struct IterationResult {
     std::vector<int8_t> built;              // the PSSM built from the last round's results
     std::vector<HitAlignment> alignments;   // the last round's results aligned against that round's scoring
+    HspLists hsps;                          // --maxHsps above 1: all alignments of those results (element 0 = `alignments`)
 };
+
+// --maxHsps above 1: all alignments of every result.  pssm: what the results were scanned with (nullptr: `letters`, which
+// are then the query; else `letters` are the consensus).  The first alignments (what is printed without --maxHsps) are element
+// 0 of every list and replace `first`.
+HspLists alignHsps(const ProgramOptions& o, HitAligner& aligner, const std::string& letters, const int8_t* pssm, const ScanResult& r,
+                   std::vector<HitAlignment>& first) {
+    const int32_t qlen = int32_t(letters.size());
+    HspLists lists = pssm ? aligner.align(pssm, qlen, letters.data(), r, o.maxHsps, o.hspMinScore)
+                          : aligner.align(letters.data(), qlen, r, o.maxHsps, o.hspMinScore);
+    first.resize(lists.size());
+    for (size_t i = 0; i < lists.size(); i++) first[i] = lists[i].front();
+    return lists;
+}
 
 // master: the query's letters (a PSSM input: the residue column of its file); first: the PSSM of round 1, or nullptr (the
 // letters).  r: in, the results of round 1; out, those of the last round.  Every round builds a PSSM from its results; round
@@ -194,8 +242,9 @@ IterationResult runIterations(const ProgramOptions& o, SearchDriver& driver, Pss
         }
         out.built = builder.build(master.data(), qlen, scoring.empty() ? nullptr : scoring.data(), r.referenceIds.data(),
                                   r.scores.data(), r.scores.size(), o.inclusionScore, o.pseudocount, &info,
-                                  o.haveInclusionEvalue ? admitted.data() : nullptr);
+                                  o.haveInclusionEvalue ? admitted.data() : nullptr, o.reportAlignments() ? o.maxHsps : 1, o.hspMinScore);
         out.alignments = std::move(info.alignments);
+        out.hsps = std::move(info.hsps);
         std::vector<int64_t> included;
         for (size_t i = 0; i < info.included.size(); i++)
             if (info.included[i]) included.push_back(r.referenceIds[i]);
@@ -257,17 +306,22 @@ void processQueryFile(const std::string& file, const ProgramOptions& o, SearchDr
         if (iteration) rounds = runIterations(o, driver, *iteration, q.num, q.sequence, nullptr, r);
         if (o.numTopOutputs > 0 || interactive) {
             std::vector<HitAlignment> alignments;
-            if (aligner && iteration) alignments = std::move(rounds.alignments);
+            HspLists lists;
+            if (aligner && iteration) {
+                alignments = std::move(rounds.alignments);
+                lists = std::move(rounds.hsps);
+            } else if (aligner && o.reportHsps()) lists = alignHsps(o, *aligner, q.sequence, nullptr, r, alignments);
             else if (aligner) alignments = aligner->align(q.sequence.data(), int32_t(q.sequence.size()), r);
             const std::vector<HitAlignment>* al = aligner ? &alignments : nullptr;
+            const HspLists* hsps = aligner && o.reportHsps() ? &lists : nullptr;
             EvalueReport evStorage;
             const EvalueReport* ev = evalueReport(o, r, evStorage);
             if (o.outputMode == ProgramOptions::OutputMode::Plain) {
                 (interactive ? std::cout : out) << "Query " << q.num << ", header" << q.header << ", length " << q.sequence.size()
                                                 << ", num overflows " << r.stats.numOverflows << "\n";
-                printScanResultPlain(out, r, driver, al, ev);
+                printScanResultPlain(out, r, driver, al, ev, hsps);
             } else {
-                printScanResultTSV(out, r, driver, interactive ? -1 : q.num, int64_t(q.sequence.size()), interactive ? "-" : q.header, al, ev);
+                printScanResultTSV(out, r, driver, interactive ? -1 : q.num, int64_t(q.sequence.size()), interactive ? "-" : q.header, al, ev, hsps);
             }
             out.flush();
             reportSignificant(o, r, driver, ev);
@@ -307,16 +361,21 @@ void processPssmQuery(const PssmQuery& q, const ProgramOptions& o, SearchDriver&
     if (iteration) rounds = runIterations(o, driver, *iteration, 0, q.consensus, q.scores.data(), r);
     if (o.numTopOutputs > 0) {
         std::vector<HitAlignment> alignments;
-        if (aligner && iteration) alignments = std::move(rounds.alignments);
+        HspLists lists;
+        if (aligner && iteration) {
+            alignments = std::move(rounds.alignments);
+            lists = std::move(rounds.hsps);
+        } else if (aligner && o.reportHsps()) lists = alignHsps(o, *aligner, q.consensus, q.scores.data(), r, alignments);
         else if (aligner) alignments = aligner->align(q.scores.data(), q.length(), q.consensus.data(), r);
         const std::vector<HitAlignment>* al = aligner ? &alignments : nullptr;
+        const HspLists* hsps = aligner && o.reportHsps() ? &lists : nullptr;
         EvalueReport evStorage;
         const EvalueReport* ev = evalueReport(o, r, evStorage);
         if (o.outputMode == ProgramOptions::OutputMode::Plain) {
             out << "Query " << 0 << ", header " << q.name << ", length " << q.length() << ", num overflows " << r.stats.numOverflows << "\n";
-            printScanResultPlain(out, r, driver, al, ev);
+            printScanResultPlain(out, r, driver, al, ev, hsps);
         } else {
-            printScanResultTSV(out, r, driver, 0, int64_t(q.length()), q.name, al, ev);
+            printScanResultTSV(out, r, driver, 0, int64_t(q.length()), q.name, al, ev, hsps);
         }
         out.flush();
         reportSignificant(o, r, driver, ev);
@@ -341,6 +400,12 @@ int main(int argc, char** argv) {
             throw std::runtime_error("--pssm cannot be combined with --alignments: use --pssmAlignments to align the results of every query, PSSM queries included");
         if (!options.pssmFiles.empty() && options.interactive)
             throw std::runtime_error("--pssm cannot be combined with --interactive");
+        if ((options.haveMaxHsps || options.haveHspMinScore) && !options.reportAlignments())
+            throw std::runtime_error("--maxHsps / --hspMinScore need --alignments or --pssmAlignments: they say how many alignments of a result are reported");
+        if (options.maxHsps < 1 || options.maxHsps > 16) throw std::runtime_error("--maxHsps must lie in 1 .. 16");
+        if (options.haveHspMinScore && options.hspMinScore < 1) throw std::runtime_error("--hspMinScore must be at least 1");
+        if (options.maxHsps > 1 && !options.haveHspMinScore)
+            throw std::runtime_error("--maxHsps above 1 needs --hspMinScore S: further alignments of a result are reported down to the raw score S");
         if (options.iterations < 1) throw std::runtime_error("--iterations must be at least 1");
         if (options.haveInclusionScore && options.haveInclusionEvalue)
             throw std::runtime_error("--inclusionScore and --inclusionEvalue cannot be combined: results go into the PSSM by one rule");
@@ -377,7 +442,7 @@ int main(int argc, char** argv) {
         }
         std::ofstream outputfile(options.outputfile);
         if (!outputfile) throw std::runtime_error("Cannot open file " + options.outputfile);
-        if (options.outputMode == ProgramOptions::OutputMode::TSV) printTSVHeader(outputfile, options.reportAlignments(), options.reportEvalues());
+        if (options.outputMode == ProgramOptions::OutputMode::TSV) printTSVHeader(outputfile, options.reportAlignments(), options.reportEvalues(), options.reportHsps());
 
         SearchDriver driver(deviceIds, options.numTopOutputs, options.matrix, options.kernels, options.memory, options.verbose,
                             options.effectiveGop(), options.effectiveGex());
@@ -443,10 +508,13 @@ int main(int argc, char** argv) {
                         ScanResult r = driver.scan(sequence.data(), int32_t(sequence.size()));
                         reportScan(options, r);
                         std::vector<HitAlignment> alignments;
-                        if (aligner) alignments = aligner->align(sequence.data(), int32_t(sequence.size()), r);
+                        HspLists lists;
+                        if (aligner && options.reportHsps()) lists = alignHsps(options, *aligner, sequence, nullptr, r, alignments);
+                        else if (aligner) alignments = aligner->align(sequence.data(), int32_t(sequence.size()), r);
                         const std::vector<HitAlignment>* al = aligner ? &alignments : nullptr;
-                        if (options.outputMode == ProgramOptions::OutputMode::Plain) printScanResultPlain(outputfile, r, driver, al);
-                        else printScanResultTSV(outputfile, r, driver, -1, int64_t(sequence.size()), "-", al);
+                        const HspLists* hsps = aligner && options.reportHsps() ? &lists : nullptr;
+                        if (options.outputMode == ProgramOptions::OutputMode::Plain) printScanResultPlain(outputfile, r, driver, al, nullptr, hsps);
+                        else printScanResultTSV(outputfile, r, driver, -1, int64_t(sequence.size()), "-", al, nullptr, hsps);
                         outputfile.flush();
                     } else {
                         std::cout << "Missing argument for command 's'\n";

@@ -34,6 +34,7 @@ void printOptions(const ProgramOptions& o) {
     for (size_t i = 0; i < o.queryFiles.size(); i++) std::cout << "queryFile " << i << " : " << o.queryFiles[i] << "\n";
     for (size_t i = 0; i < o.pssmFiles.size(); i++) std::cout << "pssmFile " << i << " : " << o.pssmFiles[i] << "\n";
     if (o.pssmAlignments) std::cout << "pssmAlignments: " << o.pssmAlignments << "\n";
+    if (o.reportHsps()) std::cout << "maxHsps: " << o.maxHsps << "\nhspMinScore: " << o.hspMinScore << "\n";
     if (o.iterations != 1) std::cout << "iterations: " << o.iterations << "\n";
     if (o.haveInclusionScore) std::cout << "inclusionScore: " << o.inclusionScore << "\n";
     if (o.haveInclusionEvalue) std::cout << "inclusionEvalue: " << o.inclusionEvalue << "\n";
@@ -80,6 +81,8 @@ bool parseArgs(int argc, char** argv, ProgramOptions& o) {
         else if (arg == "--interactive") o.interactive = true;
         else if (arg == "--alignments") o.alignments = true;
         else if (arg == "--pssmAlignments") o.pssmAlignments = true;
+        else if (arg == "--maxHsps") { o.maxHsps = std::atoi(value(i).c_str()); o.haveMaxHsps = true; }
+        else if (arg == "--hspMinScore") { o.hspMinScore = std::atoi(value(i).c_str()); o.haveHspMinScore = true; }
         else if (arg == "--iterations") o.iterations = std::atoi(value(i).c_str());
         else if (arg == "--inclusionScore") { o.inclusionScore = std::atoi(value(i).c_str()); o.haveInclusionScore = true; }
         else if (arg == "--inclusionEvalue") { o.inclusionEvalue = std::atof(value(i).c_str()); o.haveInclusionEvalue = true; }
@@ -182,6 +185,10 @@ void printHelp(char** argv) {
     std::cout << "      --tsv : Print results as tab-separated values instead of plain text. \n";
     std::cout << "      --alignments : Also report where every result aligns: query and reference begin / end, alignment length, identities, gap opens and CIGAR (computed on the GPU).\n";
     std::cout << "      --pssmAlignments : --alignments for every query, --pssm queries included. Identities and the CIGAR's = / X of a PSSM are counted against the residue column of its file.\n";
+    std::cout << "      --maxHsps N --hspMinScore S : With --alignments / --pssmAlignments: up to N (1 .. 16) non-overlapping local alignments per result\n"
+                 "        (Waterman-Eggert: the k-th shares no aligned pair with the better ones), the further ones scoring at least S (S >= 1,\n"
+                 "        needed when N > 1). TSV: one more column HSP behind CIGAR and one more line per further alignment, with its score and\n"
+                 "        coordinates; plain: one more line Alignment i.k. Ranking, --maxEvalue and inclusion look at the first alignment only.\n";
     std::cout << "      --verbose : More console output. Shows timings. \n";
     std::cout << "      --printLengthPartitions : Print number of sequences per length partition in db.\n";
     std::cout << "      --interactive : Loads DB, then waits for sequence input by user\n";

@@ -25,6 +25,13 @@ struct ProgramOptions {
     // of a PSSM against the residue column of its file)
     bool pssmAlignments = false;
     bool reportAlignments() const { return alignments || pssmAlignments; }
+    // --maxHsps N --hspMinScore S (with --alignments / --pssmAlignments; hit_alignment.hpp): up to N
+    // non-overlapping alignments per result, the further ones scoring at least S; checked in main, before any device is opened
+    bool haveMaxHsps = false;
+    int maxHsps = 1;
+    bool haveHspMinScore = false;
+    int hspMinScore = 1;
+    bool reportHsps() const { return maxHsps > 1; }
     // Iterated profile search (pssm_build.hpp; an extension): --iterations N rounds, each scanning with the PSSM built from
     // the round before's reported hits of raw score >= --inclusionScore (or by E-value: --inclusionEvalue below); --pseudocount is the
     // conversion's beta; --outPssm PREFIX writes PREFIX.<query number>.pssm

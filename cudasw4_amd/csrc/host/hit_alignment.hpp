@@ -1,6 +1,7 @@
 // hit_alignment.hpp — coordinates and CIGAR of a scan's top hits (sw_align_hits, include/cudasw4_amd.h; for the hits of a
-// PSSM query sw_align_hits_pssm, include/cudasw4_amd_pssm.h), run after SearchDriver::collect().  An extension: the
-// reference reports scores only.
+// PSSM query sw_align_hits_pssm, include/cudasw4_amd_pssm.h), run after SearchDriver::collect(); with maxHsps > 1 up to that
+// many non-overlapping alignments per hit (sw_align_hsps, include/cudasw4_amd_hsps.h).  An extension: the reference
+// reports scores only.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -43,9 +44,26 @@ public:
                                     const int32_t* scores, size_t n);
     std::vector<HitAlignment> align(const int8_t* pssm, int32_t qlen, const char* consensus, const ScanResult& r);
 
+    // Up to maxHsps (1 .. SW_MAX_HSPS) non-overlapping alignments per hit (sw_align_hsps / sw_align_hsps_pssm): one vector per
+    // hit, element 0 = the alignment the calls above return (whatever its status), then the further alignments that are
+    // SW_ALIGN_OK, best first; those scoring below minScore (>= 1) are not reported.  The trace budget is handled as above
+    // (the used pairs of a hit take (maxHsps - 1) x qlen x 4 bytes of its share of --maxTempBytes).
+    typedef std::vector<std::vector<HitAlignment>> HspLists;
+    HspLists align(const char* query, int32_t qlen, const int64_t* ids, const int32_t* scores, size_t n, int maxHsps, int minScore);
+    HspLists align(const char* query, int32_t qlen, const ScanResult& r, int maxHsps, int minScore);
+    HspLists align(const int8_t* pssm, int32_t qlen, const char* consensus, const int64_t* ids, const int32_t* scores, size_t n,
+                   int maxHsps, int minScore);
+    HspLists align(const int8_t* pssm, int32_t qlen, const char* consensus, const ScanResult& r, int maxHsps, int minScore);
+    // the same untrimmed: n x maxHsps records, slot (i, k) at i * maxHsps + k, as sw_align_hsps wrote them
+    std::vector<HitAlignment> alignSlots(const char* query, int32_t qlen, const int64_t* ids, const int32_t* scores, size_t n,
+                                         int maxHsps, int minScore);
+    std::vector<HitAlignment> alignSlots(const int8_t* pssm, int32_t qlen, const char* consensus, const int64_t* ids,
+                                         const int32_t* scores, size_t n, int maxHsps, int minScore);
+
     // What the last align() left on the device: the hits' subjects, results and CIGAR words in the layout sw_align_hits
     // was given them, for a consumer that goes on with them there (pssm_build.hpp).  All work of the aligner is complete
     // when align() returns; the pointers are valid until the next align().  n == 0: there was no such call, or no hit.
+    // After a call with maxHsps > 1 these are the hits' FIRST alignments (slot 0 of every hit, gathered into n records).
     struct Resident {
         int device = 0;
         sw_ctx* ctx = nullptr;
@@ -61,18 +79,21 @@ public:
 
 private:
     // both forms behind the encoding of the query.  pssm == nullptr: `codes` are the query's codes; else `codes` are the
-    // consensus codes (nullptr: none)
+    // consensus codes (nullptr: none).  -> n x maxHsps slots
     std::vector<HitAlignment> run(const int8_t* codes, const int8_t* pssm, int32_t qlen, const int64_t* ids,
-                                  const int32_t* scores, size_t n);
+                                  const int32_t* scores, size_t n, int maxHsps = 1, int minScore = 1);
+    std::vector<int8_t> encodeQuery(const char* query, int32_t qlen) const;
+    std::vector<int8_t> encodeConsensus(const int8_t* pssm, int32_t qlen, const char* consensus) const;
     void* grow(size_t slot, size_t bytes);
     const SearchDriver& d_;
     int device_ = 0;
     sw_ctx* ctx_ = nullptr;
     hipStream_t stream_ = nullptr;
-    enum { kQuery, kPssm, kChars, kOffsets, kLengths, kScores, kResults, kCigar, kCigarOffsets, kTemp, kBuffers };
+    enum { kQuery, kPssm, kChars, kOffsets, kLengths, kScores, kResults, kCigar, kCigarOffsets, kTemp, kFirstResults, kBuffers };
     void* buf_[kBuffers] = {};
     size_t cap_[kBuffers] = {};
     size_t residentHits_ = 0;
+    bool residentFirst_ = false;   // the last call had maxHsps > 1: resident().results are the gathered first alignments
 };
 
 }  // namespace swh

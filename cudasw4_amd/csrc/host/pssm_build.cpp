@@ -119,7 +119,7 @@ void* PssmBuilder::grow(int slot, size_t bytes) {
 
 std::vector<int8_t> PssmBuilder::build(const char* master, int32_t qlen, const int8_t* pssm, const int64_t* ids,
                                        const int32_t* scores, size_t n, int32_t minScore, double pseudocount, PssmBuildInfo* info,
-                                       const uint8_t* admitted) {
+                                       const uint8_t* admitted, int maxHsps, int hspMinScore) {
     if (qlen < 1 || !master) throw std::runtime_error("PSSM build: empty master sequence");
     if (qlen > (1 << 20)) throw std::runtime_error("PSSM build: queries longer than 2^20 residues are not supported");
     if (n > 0 && (!ids || !scores)) throw std::runtime_error("PSSM build: null hit list");
@@ -127,7 +127,14 @@ std::vector<int8_t> PssmBuilder::build(const char* master, int32_t qlen, const i
     PssmBuildInfo local;
     PssmBuildInfo& I = info ? *info : local;
     I = PssmBuildInfo();
-    I.alignments = pssm ? aligner_.align(pssm, qlen, master, ids, scores, n) : aligner_.align(master, qlen, ids, scores, n);
+    if (maxHsps > 1) {
+        I.hsps = pssm ? aligner_.align(pssm, qlen, master, ids, scores, n, maxHsps, hspMinScore)
+                      : aligner_.align(master, qlen, ids, scores, n, maxHsps, hspMinScore);
+        I.alignments.resize(n);
+        for (size_t h = 0; h < n; h++) I.alignments[h] = I.hsps[h].front();
+    } else {
+        I.alignments = pssm ? aligner_.align(pssm, qlen, master, ids, scores, n) : aligner_.align(master, qlen, ids, scores, n);
+    }
     const HitAligner::Resident res = aligner_.resident();
     if (res.n != n) throw std::runtime_error("PSSM build: internal error (resident hits)");
     // the inclusion rule

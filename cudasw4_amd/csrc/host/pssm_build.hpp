@@ -33,6 +33,8 @@ struct PssmBuildInfo {
     double lambda = 0;
     std::vector<uint8_t> included;   // one byte per hit: 1 where it took part
     std::vector<HitAlignment> alignments;   // the hits as they were aligned for this step
+    // built with maxHsps > 1: all alignments of every hit (HitAligner::HspLists; element 0 = `alignments`); else empty
+    HitAligner::HspLists hsps;
 };
 
 // One step of an iterated search on the aligner's device, stream and buffers: the hits' subjects, results and CIGARs stay
@@ -47,8 +49,11 @@ public:
     // master: the original query's letters (for a PSSM input the residue column of its file).  pssm: nullptr when the hits
     // were scanned with the letters, else the qlen x 21 PSSM they were scanned with.  admitted: nullptr, or one byte per hit
     // that takes the place of the score test (inclusion by E-value: 0 = left out, counted in belowScore).  -> qlen x 21 int8
+    // maxHsps > 1: the hits are aligned with up to maxHsps alignments each, the further ones scoring at least hspMinScore
+    // (info->hsps); the PSSM is built from the first alignments (HitAligner::resident()) and is the one of maxHsps == 1.
     std::vector<int8_t> build(const char* master, int32_t qlen, const int8_t* pssm, const int64_t* ids, const int32_t* scores,
-                              size_t n, int32_t minScore, double pseudocount, PssmBuildInfo* info, const uint8_t* admitted = nullptr);
+                              size_t n, int32_t minScore, double pseudocount, PssmBuildInfo* info, const uint8_t* admitted = nullptr,
+                              int maxHsps = 1, int hspMinScore = 1);
 
 private:
     void* grow(int slot, size_t bytes);

@@ -24,7 +24,7 @@ EXPORTS = ["swdrv_last_error", "swdrv_create", "swdrv_destroy", "swdrv_open_db",
            "swdrv_bind_to_numa_node", "swdrv_device_numa_node", "swdrv_window_stats", "swdrv_service_launches",
            "swdrv_tail_overlaps", "swdrv_prefers_two_in_flight", "swdrv_pipeline_launches", "swdrv_handshake_active", "swdrv_preferred_in_flight",
            "swdrv_latency_scans", "swdrv_plan_runs_mode", "swdrv_align_hits", "swdrv_scan_pssm", "swdrv_scan_submit_pssm",
-           "swdrv_align_hits_pssm", "swdrv_pssm_from_counts", "swdrv_build_pssm", "swdrv_write_pssm_ascii",
+           "swdrv_align_hits_pssm", "swdrv_align_hsps", "swdrv_align_hsps_pssm", "swdrv_pssm_from_counts", "swdrv_build_pssm", "swdrv_write_pssm_ascii",
            "swdrv_set_statistics", "swdrv_last_statistics", "swdrv_stats_from_histogram", "swdrv_evalues", "swdrv_length_bin",
            "swdrv_set_ranking", "swdrv_last_ranking", "swdrv_zscore_for_evalue", "swdrv_rank_order"]
 
@@ -136,6 +136,42 @@ def _align_pssm_fn():
         vp = ctypes.c_void_p
         f.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_char_p, vp, vp, ctypes.c_int, vp, vp, ctypes.c_int64]
     return f
+
+
+def _align_hsps_fns():
+    """swdrv_align_hsps / swdrv_align_hsps_pssm, bound on first use (like swdrv_align_hits: not in every build of this C ABI)"""
+    f, g = lib.swdrv_align_hsps, lib.swdrv_align_hsps_pssm
+    if f.argtypes is None:
+        vp, i = ctypes.c_void_p, ctypes.c_int
+        f.argtypes = [vp, ctypes.c_char_p, ctypes.c_int32, vp, vp, i, i, i, vp, vp, ctypes.c_int64]
+        g.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_char_p, vp, vp, i, i, i, vp, vp, ctypes.c_int64]
+    return f, g
+
+
+def _hsp_lists(res, cigar, n, max_hsps):
+    """the n * max_hsps slots of swdrv_align_hsps as one list per hit: slot 0 whatever it is, then the slots that are OK.
+    -> [[(record, CIGAR string)]]"""
+    from . import capi
+    out = []
+    for i in range(n):
+        hit = []
+        for k in range(max_hsps):
+            r = res[i * max_hsps + k]
+            if k and int(r["status"]) != capi.ALIGN_OK:
+                break
+            hit.append((r, capi.cigar_string(cigar[int(r["cigar_offset"]):int(r["cigar_offset"]) + int(r["cigar_len"])])))
+        out.append(hit)
+    return out
+
+
+def _check_hsps(max_hsps, min_score):
+    from . import capi
+    if not 1 <= int(max_hsps) <= capi.MAX_HSPS:
+        raise ValueError("max_hsps must lie in [1, %d]" % capi.MAX_HSPS)
+    if max_hsps > 1 and min_score is None:
+        raise ValueError("max_hsps > 1 needs min_score: the least score of a further alignment")
+    if min_score is not None and int(min_score) < 1:
+        raise ValueError("min_score must be at least 1")
 
 
 def _pssm_fns():
@@ -692,15 +728,26 @@ class Driver:
             out.append(self.collect())
         return out
 
-    def align_hits(self, query_letters, result):
+    def align_hits(self, query_letters, result, max_hsps=1, min_score=None):
         """Coordinates, counts and CIGAR of the hits of a scan/collect result of `query_letters` (swdrv_align_hits).
-        -> (structured array of capi.align_result_dtype(), list of CIGAR strings, "*" where there is none)"""
+        -> (structured array of capi.align_result_dtype(), list of CIGAR strings, "*" where there is none)
+        max_hsps > 1 (swdrv_align_hsps; min_score is then required): up to that many non-overlapping alignments per hit, the
+        further ones scoring at least min_score.  -> one list per hit of (record, CIGAR string): the hit's first alignment
+        (whatever its status), then its further alignments, best first."""
         from . import capi
+        _check_hsps(max_hsps, min_score)
         if isinstance(query_letters, str):
             query_letters = query_letters.encode()
         ids = np.ascontiguousarray(result["ids"], dtype=np.int64)
         scores = np.ascontiguousarray(result["scores"], dtype=np.int32)
         n = len(ids)
+        if max_hsps > 1:
+            res = np.zeros(n * max_hsps, dtype=capi.align_result_dtype())
+            cap = max_hsps * sum(len(query_letters) + self.reference_length(int(i)) for i in ids)
+            cigar = np.zeros(max(cap, 1), dtype=np.uint32)
+            _check(_align_hsps_fns()[0](self.handle, query_letters, len(query_letters), ids.ctypes.data, scores.ctypes.data, n,
+                                        max_hsps, min_score, res.ctypes.data, cigar.ctypes.data, cap))
+            return _hsp_lists(res, cigar, n, max_hsps)
         res = np.zeros(n, dtype=capi.align_result_dtype())
         cap = sum(len(query_letters) + self.reference_length(int(i)) for i in ids)
         cigar = np.zeros(max(cap, 1), dtype=np.uint32)
@@ -709,11 +756,13 @@ class Driver:
         cigars = [capi.cigar_string(cigar[int(r["cigar_offset"]):int(r["cigar_offset"]) + int(r["cigar_len"])]) for r in res]
         return res, cigars
 
-    def align_hits_pssm(self, pssm, result, consensus=None):
+    def align_hits_pssm(self, pssm, result, consensus=None, max_hsps=1, min_score=None):
         """align_hits for the hits of a scan_pssm / submit_pssm result of `pssm` (swdrv_align_hits_pssm).  consensus: one
         residue letter per position, which identities and '=' / 'X' are counted against (a non-standard letter is identical
-        to nothing); None: the best-scoring standard residue of every row (pssm.consensus_of).  Returns what align_hits returns."""
+        to nothing); None: the best-scoring standard residue of every row (pssm.consensus_of).  Returns what align_hits returns,
+        with max_hsps > 1 (swdrv_align_hsps_pssm) its lists."""
         from . import capi, pssm as _pssm
+        _check_hsps(max_hsps, min_score)
         m = _pssm.as_pssm(pssm)
         qlen = m.shape[0]
         if consensus is not None:
@@ -724,6 +773,13 @@ class Driver:
         ids = np.ascontiguousarray(result["ids"], dtype=np.int64)
         scores = np.ascontiguousarray(result["scores"], dtype=np.int32)
         n = len(ids)
+        if max_hsps > 1:
+            res = np.zeros(n * max_hsps, dtype=capi.align_result_dtype())
+            cap = max_hsps * sum(qlen + self.reference_length(int(i)) for i in ids)
+            cigar = np.zeros(max(cap, 1), dtype=np.uint32)
+            _check(_align_hsps_fns()[1](self.handle, m.ctypes.data, qlen, consensus, ids.ctypes.data, scores.ctypes.data, n,
+                                        max_hsps, min_score, res.ctypes.data, cigar.ctypes.data, cap))
+            return _hsp_lists(res, cigar, n, max_hsps)
         res = np.zeros(n, dtype=capi.align_result_dtype())
         cap = sum(qlen + self.reference_length(int(i)) for i in ids)
         cigar = np.zeros(max(cap, 1), dtype=np.uint32)

@@ -189,6 +189,17 @@ int swdrv_align_hits(swdrv* d, const char* query, int32_t qlen, const int64_t* i
  * every row, the first of equals.  Gap scores, trace budget, outputs and errors as above; the driver's matrix is not used. */
 int swdrv_align_hits_pssm(swdrv* d, const int8_t* pssm, int32_t qlen, const char* consensus, const int64_t* ids,
                           const int32_t* scores, int n, sw_align_result* results, uint32_t* cigar, int64_t cigar_cap);
+/* Up to max_hsps (1 .. 16) non-overlapping local alignments per hit (sw_align_hsps / sw_align_hsps_pssm,
+ * include/cudasw4_amd_hsps.h).  results: n * max_hsps records, slot (i, k) at i * max_hsps + k: slot 0 is the
+ * record of the calls above; alignments k >= 1 that score below min_score (>= 1) are not reported (SW_ALIGN_EMPTY from there
+ * on); behind a slot without traceback the slots are SW_ALIGN_NOT_COMPUTED (5).  cigar: the CIGARs of all slots back to
+ * back (max_hsps * (qlen + length) words per hit always suffice).  Everything else as above; the used pairs of a hit take
+ * (max_hsps - 1) * qlen * 4 bytes of its share of max_temp_bytes. */
+int swdrv_align_hsps(swdrv* d, const char* query, int32_t qlen, const int64_t* ids, const int32_t* scores, int n, int max_hsps,
+                     int min_score, sw_align_result* results, uint32_t* cigar, int64_t cigar_cap);
+int swdrv_align_hsps_pssm(swdrv* d, const int8_t* pssm, int32_t qlen, const char* consensus, const int64_t* ids,
+                          const int32_t* scores, int n, int max_hsps, int min_score, sw_align_result* results, uint32_t* cigar,
+                          int64_t cigar_cap);
 
 /* Building a PSSM from a query's aligned hits (an extension; DESIGN.md, "Building a PSSM"): the step between two rounds of
  * an iterated profile search.
