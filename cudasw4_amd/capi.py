@@ -44,6 +44,8 @@ RANK_KEY_NONE = -3.0e38   # as float32: the key of a subject that was not scored
 # ... and include/cudasw4_amd_hsps.h (hit alignment: up to MAX_HSPS non-overlapping local alignments per hit)
 HSPS_EXPORTS = ["sw_align_hsps", "sw_align_hsps_pssm"]
 MAX_HSPS = 16
+# ... and include/cudasw4_amd_shuffle.h (statistics calibrated on shuffled subjects: replicas of a block, every subject permuted)
+SHUFFLE_EXPORTS = ["sw_shuffle_subjects"]
 
 
 # sw_align_hits (include/cudasw4_amd.h): result records, statuses, flags, CIGAR op codes
@@ -153,6 +155,8 @@ def _load():
         dbl = ctypes.c_double
         L.sw_zscore_keys.argtypes = [vp, vp, vp, i64, dbl, dbl, dbl, dbl, vp, vp, vp, vp]
         L.sw_gather_hits.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, vp, vp]
+    if hasattr(L, "sw_shuffle_subjects"):
+        L.sw_shuffle_subjects.argtypes = [vp, vp, vp, vp, vp, i32, ctypes.c_uint32, i32, i32, vp, sz, vp]
     return L
 
 
@@ -425,6 +429,18 @@ def gather_hits(ctx, positions, k, scores, ids, out_scores, out_ids, stream=0):
         raise SwError(-1, "this build of libcudasw4_amd.so has no sw_gather_hits")
     check(lib.sw_gather_hits(ctx.handle if ctx is not None else None, positions or None, k, scores or None, ids or None,
                              out_scores or None, out_ids or None, stream or None))
+
+
+def shuffle_subjects(ctx, chars, offsets, lengths, n, seed, out, replica_stride, keys=0, first_replica=0, replicas=1, stream=0):
+    """sw_shuffle_subjects (include/cudasw4_amd_shuffle.h): replicas first_replica .. first_replica + replicas - 1 of the n
+    subjects (chars, offsets, lengths: dbdata layout) to out, replica r of the call at out + r * replica_stride, subject i
+    permuted with the key of (seed, keys[i] or the position i, first_replica + r), padding bytes code 20.  Every buffer is a
+    device pointer as an integer.  Asynchronous on `stream` behind a read-back of the block's two ends."""
+    if not hasattr(lib, "sw_shuffle_subjects"):
+        raise SwError(-1, "this build of libcudasw4_amd.so has no sw_shuffle_subjects")
+    check(lib.sw_shuffle_subjects(ctx.handle if ctx is not None else None, chars or None, offsets or None, lengths or None,
+                                  keys or None, n, seed & 0xFFFFFFFF, first_replica, replicas, out or None, replica_stride,
+                                  stream or None))
 
 
 def topk_temp_bytes(n, k):

@@ -26,6 +26,7 @@
 #include "search_rank.hpp"
 #include "search_stats.hpp"
 #include "sequence_reader.hpp"
+#include "shuffle_stats.hpp"
 
 using namespace swh;
 
@@ -166,16 +167,38 @@ void reportScan(const ProgramOptions& o, const ScanResult& r) {
     else std::cout << "Done.\n";
 }
 
-// the fit of a scan made with the statistics on (--evalues / --maxEvalue / --inclusionEvalue)
+// --statistics shuffled: the calibrator and the calibration of the query in flight (one at a time).  Every query, and every
+// round's PSSM, is calibrated right before it is submitted; under --rankBy evalue the driver ranks it by that fit.
+struct ShuffledStatistics {
+    std::unique_ptr<ShuffleCalibrator> calibrator;
+    SearchStats current;
+    void finish(SearchDriver& driver, const std::unique_ptr<Calibration>& c, bool ranked) {
+        current = c->stats;
+        if (ranked) {
+            RankFit f;
+            f.ok = current.fitted(); f.a = current.a; f.b1 = current.b1; f.sd = current.sd;
+            driver.setRankFit(&f);
+        }
+    }
+    void beforeSubmit(SearchDriver& driver, const char* letters, int32_t qlen, bool ranked) { finish(driver, calibrator->calibrate(letters, qlen), ranked); }
+    void beforeSubmit(SearchDriver& driver, const int8_t* pssm, int32_t qlen, bool ranked) { finish(driver, calibrator->calibrate(pssm, qlen), ranked); }
+};
+ShuffledStatistics* shuffled = nullptr;   // (non-null under --statistics shuffled)
+
+// the fit of a scan made with the statistics on (--evalues / --maxEvalue / --inclusionEvalue): of the scan's own table, or
+// under --statistics shuffled the query's calibration with N from the scan's table
 SearchStats fitOf(const ScanResult& r) {
     if (r.table.empty()) throw std::runtime_error("internal error: a scan without its score table");
+    if (shuffled) return calibrated_stats(shuffled->current, table_count(r.table.front()));
     return stats_from_table(r.table.front());
 }
 
 void reportStatistics(const ProgramOptions& o, const SearchStats& s) {
     if (!o.verbose) return;
-    if (!s.fitted()) std::cout << "statistics: no fit\n";
-    else std::cout << "statistics: N " << s.N << " fitted on " << s.nIncluded << " a " << s.a << " b " << s.b1 << " sd " << s.sd
+    std::cout << "statistics: ";
+    if (shuffled) std::cout << "shuffled " << shuffled->calibrator->subjects() << " subjects x " << shuffled->calibrator->replicas() << ", ";
+    if (!s.fitted()) std::cout << "no fit\n";
+    else std::cout << "N " << s.N << " fitted on " << s.nIncluded << " a " << s.a << " b " << s.b1 << " sd " << s.sd
                    << " rounds " << s.rounds << "\n";
 }
 
@@ -259,6 +282,7 @@ IterationResult runIterations(const ProgramOptions& o, SearchDriver& driver, Pss
         if (round >= o.iterations || converged) break;
         previous = std::move(included);
         scoring = out.built;
+        if (shuffled) shuffled->beforeSubmit(driver, scoring.data(), qlen, o.rankByEvalue());
         submit_pssm(driver, scoring.data(), qlen);
         r = driver.collect();
     }
@@ -291,6 +315,7 @@ void processQueryFile(const std::string& file, const ProgramOptions& o, SearchDr
     auto max_in_flight = [&](size_t queryLength) {
         if (iteration) return 1;   // the rounds of a query are scans of their own: nothing else may be in flight
         if (o.rankByEvalue()) return 1;   // the second half of a ranked query reads its score array again (SearchDriver::setRanking)
+        if (shuffled) return 1;           // one calibration at a time
         if (pipe) return pipe[0] == '1' ? 2 : 1;
         return driver.preferredInFlight(int32_t(std::min<size_t>(queryLength, size_t(INT32_MAX))));
     };
@@ -330,6 +355,7 @@ void processQueryFile(const std::string& file, const ProgramOptions& o, SearchDr
     try {
         while (reader.next()) {
             pending.push_back(Pending{query_num++, reader.header(), reader.sequence()});
+            if (shuffled) shuffled->beforeSubmit(driver, pending.back().sequence.data(), int32_t(pending.back().sequence.size()), o.rankByEvalue());
             driver.submit(pending.back().sequence.data(), int32_t(pending.back().sequence.size()));
             const int maxInFlight = max_in_flight(pending.back().sequence.size());
             while (driver.inFlight() >= maxInFlight) finish_oldest();
@@ -354,6 +380,7 @@ void processPssmQuery(const PssmQuery& q, const ProgramOptions& o, SearchDriver&
     driver.totalTimerStart();
     std::cout << "Processing query " << 0 << " ... ";
     std::cout.flush();
+    if (shuffled) shuffled->beforeSubmit(driver, q.scores.data(), q.length(), o.rankByEvalue());
     submit_pssm(driver, q.scores.data(), q.length());
     ScanResult r = driver.collect();
     reportScan(o, r);
@@ -414,6 +441,15 @@ int main(int argc, char** argv) {
                                      "at least S) or --inclusionEvalue X (by their E-values, at most X)");
         if (options.rankBy != "score" && options.rankBy != "evalue")
             throw std::runtime_error("--rankBy must be score or evalue, not '" + options.rankBy + "'");
+        if (options.statistics != "scan" && options.statistics != "shuffled")
+            throw std::runtime_error("--statistics must be scan or shuffled, not '" + options.statistics + "'");
+        if ((options.haveShuffles || options.haveShuffleSubjects || options.haveShuffleSeed) && !options.shuffledStatistics())
+            throw std::runtime_error("--shuffles / --shuffleSubjects / --shuffleSeed need --statistics shuffled: they say what the statistics are calibrated on");
+        if (options.haveShuffles && (options.shuffles < 1 || options.shuffles > kShuffleMaxReplicas)) throw std::runtime_error("--shuffles must lie in 1 .. 64");
+        if (options.haveShuffleSubjects && (options.shuffleSubjects < 1 || options.shuffleSubjects > INT32_MAX))
+            throw std::runtime_error("--shuffleSubjects must be at least 1");
+        if (options.haveShuffleSeed && options.shuffleSeed > UINT32_MAX) throw std::runtime_error("--shuffleSeed must lie in 0 .. 4294967295");
+        if (options.shuffledStatistics() && options.interactive) throw std::runtime_error("--statistics shuffled cannot be combined with --interactive");
         if (options.haveMaxEvalue && !(options.maxEvalue >= 0)) throw std::runtime_error("--maxEvalue must not be negative");
         if (options.haveInclusionEvalue && !(options.inclusionEvalue >= 0)) throw std::runtime_error("--inclusionEvalue must not be negative");
         if (options.wantStatistics() && options.interactive) throw std::runtime_error("--evalues / --maxEvalue / --inclusionEvalue / --rankBy evalue cannot be combined with --interactive");
@@ -468,6 +504,12 @@ int main(int argc, char** argv) {
         if (options.loadFullDBToGpu) driver.prefetchDBToGpus();
         if (options.wantStatistics()) enable_statistics(driver, true);
         if (options.rankByEvalue()) set_ranking(driver, true, options.haveMaxEvalue ? options.maxEvalue : 0.0);
+        ShuffledStatistics shuffledStorage;
+        if (options.shuffledStatistics()) {
+            shuffledStorage.calibrator = std::make_unique<ShuffleCalibrator>(driver, int32_t(options.shuffleSubjects), int32_t(options.shuffles),
+                                                                             uint32_t(options.shuffleSeed));
+            shuffled = &shuffledStorage;
+        }
         std::unique_ptr<HitAligner> aligner;
         if (options.reportAlignments() || options.buildsPssm()) aligner = std::make_unique<HitAligner>(driver);
         std::unique_ptr<PssmBuilder> iteration;   // (non-null: every query goes through its rounds)

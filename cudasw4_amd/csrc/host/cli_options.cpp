@@ -42,6 +42,10 @@ void printOptions(const ProgramOptions& o) {
     if (o.reportEvalues()) std::cout << "evalues: 1\n";
     if (o.haveMaxEvalue) std::cout << "maxEvalue: " << o.maxEvalue << "\n";
     if (o.haveRankBy) std::cout << "rankBy: " << o.rankBy << "\n";
+    if (o.haveStatistics) std::cout << "statistics: " << o.statistics << "\n";
+    if (o.haveShuffles) std::cout << "shuffles: " << o.shuffles << "\n";
+    if (o.haveShuffleSubjects) std::cout << "shuffleSubjects: " << o.shuffleSubjects << "\n";
+    if (o.haveShuffleSeed) std::cout << "shuffleSeed: " << o.shuffleSeed << "\n";
     if (!o.outPssm.empty()) std::cout << "outPssm: " << o.outPssm << "\n";
     std::cout << "blosum: " << substitution_matrix(o.matrix).name << "\n";
     std::cout << "singlePassType: " << to_string(o.kernels.singlePassType) << "\n";
@@ -89,6 +93,10 @@ bool parseArgs(int argc, char** argv, ProgramOptions& o) {
         else if (arg == "--evalues") o.evalues = true;
         else if (arg == "--maxEvalue") { o.maxEvalue = std::atof(value(i).c_str()); o.haveMaxEvalue = true; }
         else if (arg == "--rankBy") { o.rankBy = value(i); o.haveRankBy = true; }
+        else if (arg == "--statistics") { o.statistics = value(i); o.haveStatistics = true; }
+        else if (arg == "--shuffles") { o.shuffles = std::atoll(value(i).c_str()); o.haveShuffles = true; }
+        else if (arg == "--shuffleSubjects") { o.shuffleSubjects = std::atoll(value(i).c_str()); o.haveShuffleSubjects = true; }
+        else if (arg == "--shuffleSeed") { o.shuffleSeed = std::strtoull(value(i).c_str(), nullptr, 10); o.haveShuffleSeed = true; }
         else if (arg == "--pseudocount") o.pseudocount = std::atof(value(i).c_str());
         else if (arg == "--outPssm") o.outPssm = value(i);
         else if (arg == "--printLengthPartitions") o.printLengthPartitions = true;
@@ -172,7 +180,17 @@ void printHelp(char** argv) {
     std::cout << "      --rankBy score|evalue : What the --top list is ranked by. Default: score. evalue implies --evalues: the list holds the\n"
                  "        results of smallest E-value (largest Z-score) of the whole DB, not the best raw scores, which favour long subjects;\n"
                  "        queries are scanned one at a time. With --maxEvalue X and --verbose, also the number of subjects of the DB with an\n"
-                 "        E-value of at most X. The raw-score list where the scan allows no fit.\n\n";
+                 "        E-value of at most X. The raw-score list where the scan allows no fit.\n";
+    std::cout << "      --statistics scan|shuffled : What the Z-scores and E-values are fitted on. Default: scan, the scan's own scores, which\n"
+                 "        assumes that almost every subject is unrelated to the query. shuffled implies --evalues: every query is also scored\n"
+                 "        against a sample of the DB whose subjects' residues are permuted on the GPU (length and composition kept, homology\n"
+                 "        destroyed) and the fit is made on those scores - for DBs dominated by one family, and for DBs too small to fit.\n"
+                 "        Queries are scanned one at a time.\n";
+    std::cout << "      --shuffleSubjects M : With --statistics shuffled: the sample holds at most M subjects, evenly spread over the DB's length\n"
+                 "        order. Default: 10000.\n";
+    std::cout << "      --shuffles R : With --statistics shuffled: every subject of the sample is permuted R times (1 .. 64). Default: as many as\n"
+                 "        bring 2000 scores, 1 .. 64.\n";
+    std::cout << "      --shuffleSeed S : With --statistics shuffled: seed of the permutations. Default: 1.\n\n";
     std::cout << "   Memory\n";
     std::cout << "      --maxGpuMem val : Try not to use more than val bytes of gpu memory per gpu. Uses all available gpu memory by default\n";
     std::cout << "      --maxTempBytes val : Size of temp storage in GPU memory. Can use suffix K,M,G. Default val = " << d.memory.maxTempBytes << "\n";

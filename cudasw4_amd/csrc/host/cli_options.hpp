@@ -54,7 +54,17 @@ struct ProgramOptions {
     bool haveRankBy = false;
     std::string rankBy = "score";
     bool rankByEvalue() const { return rankBy == "evalue"; }
-    bool reportEvalues() const { return evalues || haveMaxEvalue || rankByEvalue(); }
+    // --statistics scan|shuffled (shuffle_stats.hpp; an extension): shuffled fits every query's statistics on its scores against
+    // a sample of the DB with permuted subjects (--shuffleSubjects M of them, --shuffles R times each, --shuffleSeed S), implies
+    // --evalues and scans one query at a time; the values are checked in main, before any device is opened
+    bool haveStatistics = false;
+    std::string statistics = "scan";
+    bool haveShuffles = false, haveShuffleSubjects = false, haveShuffleSeed = false;
+    long long shuffles = 0;            // 0: ceil(2000 / sample) clamped to 1 .. 64
+    long long shuffleSubjects = 10000;
+    unsigned long long shuffleSeed = 1;
+    bool shuffledStatistics() const { return statistics == "shuffled"; }
+    bool reportEvalues() const { return evalues || haveMaxEvalue || rankByEvalue() || shuffledStatistics(); }
     bool wantStatistics() const { return reportEvalues() || haveInclusionEvalue; }
     bool prefetchDBFile = false;
     int numTopOutputs = 10;

@@ -1504,6 +1504,12 @@ void SearchDriver::setRanking(const RankHooks* hooks, double maxEvalue) {
     rankMaxEvalue_ = hooks && maxEvalue > 0 ? maxEvalue : 0;
 }
 
+void SearchDriver::setRankFit(const RankFit* fit) {
+    if (pendingCount_) throw std::runtime_error("setRankFit with queries in flight: collect() them first");
+    haveNextRankFit_ = fit != nullptr;
+    if (fit) nextRankFit_ = *fit;
+}
+
 void SearchDriver::submit(const char* query, int32_t queryLength) {
     check_submit(db_.get(), queryLength, pendingCount_);
     encodedQuery_.resize(size_t(queryLength));
@@ -1542,6 +1548,9 @@ ScanResult SearchDriver::collect() {
     TraceRange traceCollect("collect query of %d residues", int(ps.qlen));
     pendingHead_ = (pendingHead_ + 1) % kMaxInFlight;
     pendingCount_--;
+    const bool haveNextRankFit = haveNextRankFit_;   // (for this query alone, whatever becomes of it)
+    const RankFit nextRankFit = nextRankFit_;
+    haveNextRankFit_ = false;
     std::exception_ptr first;
     for (auto& gp : gpus_) {  // plain waits: no need for the worker threads
         try { finishOnGpu(*gp, ps.slot, ps.qlen); } catch (...) { if (!first) first = std::current_exception(); }
@@ -1564,7 +1573,13 @@ ScanResult SearchDriver::collect() {
     // E-value ranking: the fit of the whole DB's table, then each GPU's candidates by Z-score key (setRanking)
     RankFit fit;
     if (ps.ranked) {
-        fit = rankHooks_->fit(result.table.front());
+        if (haveNextRankFit) {   // a fit made elsewhere (setRankFit): N is this scan's all the same
+            fit = nextRankFit;
+            fit.N = 0;
+            for (uint32_t cell : result.table.front().hist) fit.N += int64_t(cell);
+        } else {
+            fit = rankHooks_->fit(result.table.front());
+        }
         const bool threshold = fit.ok && rankMaxEvalue_ > 0;
         double zMin = -DBL_MAX;
         if (threshold) {

@@ -244,6 +244,10 @@ public:
     // beyond what a scan did before.  Not with queries in flight.
     void setRanking(const RankHooks* hooks, double maxEvalue);
     bool ranksByEvalue() const { return rankHooks_ != nullptr; }
+    // A fit for the NEXT collected query (statistics calibrated elsewhere, shuffle_stats.hpp): when set, the
+    // ranked half of that query's collect() uses fit->ok, a, b1 and sd, with N from the query's own table, instead of
+    // hooks->fit(table); collect() clears it.  nullptr: clear.  Without it nothing changes.  Not with queries in flight.
+    void setRankFit(const RankFit* fit);
     ScanResult collect();
     int inFlight() const { return int(pendingCount_); }
 
@@ -253,6 +257,8 @@ public:
     std::string_view getReferenceHeader(int64_t id) const { return db_->header(size_t(id - idBase_)); }
     int32_t getReferenceLength(int64_t id) const { return db_->length(size_t(id - idBase_)); }
     std::string getReferenceSequence(int64_t id) const { return db_->sequence_letters(size_t(id - idBase_)); }
+    size_t numSequences() const { return db_ ? db_->num_sequences() : 0; }   // of the whole DB the driver opened, whatever its shard
+    int64_t idBase() const { return idBase_; }
     void printDBInfo() const;              // cudasw4.cuh:799-807
     void printDBLengthPartitions() const;  // cudasw4.cuh:809-816
     int numGpus() const { return int(gpus_.size()); }
@@ -341,6 +347,8 @@ private:
     ScoreTapFn scoreTap_ = nullptr;
     const RankHooks* rankHooks_ = nullptr;
     double rankMaxEvalue_ = 0;
+    RankFit nextRankFit_;             // setRankFit: the fit of the next collected query
+    bool haveNextRankFit_ = false;
     double scanT0_ = 0;
     double watchdogSeconds_ = 60.0;   // CUDASW4_AMD_WATCHDOG_SECONDS: base of collect()'s deadline (0: none)
     // queries submitted and not yet collected, oldest first (a ring of kMaxInFlight result slots per GPU)

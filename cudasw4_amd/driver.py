@@ -26,7 +26,9 @@ EXPORTS = ["swdrv_last_error", "swdrv_create", "swdrv_destroy", "swdrv_open_db",
            "swdrv_latency_scans", "swdrv_plan_runs_mode", "swdrv_align_hits", "swdrv_scan_pssm", "swdrv_scan_submit_pssm",
            "swdrv_align_hits_pssm", "swdrv_align_hsps", "swdrv_align_hsps_pssm", "swdrv_pssm_from_counts", "swdrv_build_pssm", "swdrv_write_pssm_ascii",
            "swdrv_set_statistics", "swdrv_last_statistics", "swdrv_stats_from_histogram", "swdrv_evalues", "swdrv_length_bin",
-           "swdrv_set_ranking", "swdrv_last_ranking", "swdrv_zscore_for_evalue", "swdrv_rank_order"]
+           "swdrv_set_ranking", "swdrv_last_ranking", "swdrv_zscore_for_evalue", "swdrv_rank_order",
+           "swdrv_calibrate_shuffled", "swdrv_calibrate_shuffled_pssm", "swdrv_set_rank_fit", "swdrv_shuffle_sample",
+           "swdrv_shuffle_replicas", "swdrv_shuffle_permutation"]
 
 
 class DriverError(RuntimeError):
@@ -237,6 +239,25 @@ def _stats_struct(stats):
                   int(stats["rounds"]), int(stats["status"]))
 
 
+SHUFFLE_DEFAULT_SUBJECTS, SHUFFLE_MAX_REPLICAS = 10000, 64
+
+
+def _shuffle_fns():
+    """swdrv_calibrate_shuffled / swdrv_calibrate_shuffled_pssm / swdrv_set_rank_fit / swdrv_shuffle_sample /
+    swdrv_shuffle_replicas / swdrv_shuffle_permutation, bound on first use (not in every build of this C ABI)"""
+    cal, calp, setfit, sample, reps, perm = (lib.swdrv_calibrate_shuffled, lib.swdrv_calibrate_shuffled_pssm, lib.swdrv_set_rank_fit,
+                                            lib.swdrv_shuffle_sample, lib.swdrv_shuffle_replicas, lib.swdrv_shuffle_permutation)
+    if cal.argtypes is None:
+        vp, i32, i64, u32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32
+        cal.argtypes = [vp, ctypes.c_char_p, i32, i32, i32, u32, ctypes.POINTER(_Stats), vp, vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+        calp.argtypes = [vp, vp, i32, i32, i32, u32, ctypes.POINTER(_Stats), vp, vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+        setfit.argtypes = [vp, ctypes.POINTER(_Stats)]
+        sample.argtypes = [i64, i64, vp]
+        reps.argtypes = [i64, i32]
+        perm.argtypes = [i32, u32, i64, i32, vp]
+    return cal, calp, setfit, sample, reps, perm
+
+
 RANK_SCORE, RANK_EVALUE = 0, 1
 
 
@@ -434,6 +455,9 @@ class Driver:
         self.handle = h
         self.num_top = num_top
         self.statistics = False
+        self.statistics_mode = "scan"
+        self._shuffle = (None, SHUFFLE_DEFAULT_SUBJECTS, 1)   # shuffles, max_subjects, seed of mode "shuffled"
+        self._calibrations = []                                # of the queries in flight, oldest first (mode "shuffled")
         self.ranking = "score"
         self.max_evalue = None
 
@@ -464,14 +488,70 @@ class Driver:
         _check(_rank_fns()[1](self.handle, ctypes.byref(c), ctypes.byref(z)))
         return int(c.value), float(z.value)
 
-    def set_statistics(self, on=True):
+    def set_statistics(self, on=True, mode="scan", shuffles=None, max_subjects=SHUFFLE_DEFAULT_SUBJECTS, seed=1):
         """Search statistics: from now on every scan also histograms its scores on the GPU, and the dicts of
         scan / scan_pssm / collect carry "zscores" and "evalues" (float64, aligned with "scores") and "stats" (the fit: a, b1,
-        sd, n_included, N, rounds, status; plus the table: hist, sumlen).  Not with queries in flight."""
+        sd, n_included, N, rounds, status, mode; plus the table: hist, sumlen).  Not with queries in flight.
+        mode "shuffled" (DESIGN.md §15): the fit is made on the scores of the query against a sample of at most max_subjects
+        subjects of the DB, each permuted `shuffles` times (None: ceil(2000 / sample) clamped to [1, 64]) under `seed` — every
+        query is calibrated (calibrate()) when it is submitted; "stats" then holds that fit with N from the scan's table, the
+        calibration's hist and sumlen, and "subjects" / "replicas"; under set_ranking("evalue") the list is ranked by it."""
+        if mode not in ("scan", "shuffled"):
+            raise ValueError("statistics mode must be 'scan' or 'shuffled', not %r" % (mode,))
+        if shuffles is not None and not 1 <= int(shuffles) <= SHUFFLE_MAX_REPLICAS:
+            raise ValueError("shuffles must lie in [1, %d]" % SHUFFLE_MAX_REPLICAS)
+        if int(max_subjects) < 1:
+            raise ValueError("max_subjects must be at least 1")
         if not on and self.ranking == "evalue":
             raise ValueError("ranking by E-value needs the statistics: set_ranking('score') first")
+        if self._calibrations:
+            raise DriverError("set_statistics with queries in flight: collect() them first")
         _check(_stats_fns()[0](self.handle, int(bool(on))))
         self.statistics = bool(on)
+        self.statistics_mode = mode if on else "scan"
+        self._shuffle = (None if shuffles is None else int(shuffles), int(max_subjects), int(seed) & 0xFFFFFFFF)
+
+    def calibrate(self, query_or_pssm, shuffles=None, max_subjects=None, seed=None):
+        """The shuffled calibration of one query (swdrv_calibrate_shuffled): residue letters (str / bytes) or a
+        PSSM ((qlen, 21) int8).  -> the fit dict (a, b1, sd, n_included, N = subjects x replicas, rounds, status) with the
+        calibration's table (hist, sumlen), "subjects" and "replicas".  Depends on the query and the DB only: it may run
+        while a scan is in flight.  The parameters default to those of set_statistics."""
+        sh, ms, sd = self._shuffle
+        sh = sh if shuffles is None else int(shuffles)
+        ms = ms if max_subjects is None else int(max_subjects)
+        sd = sd if seed is None else int(seed) & 0xFFFFFFFF
+        s, m, r = _Stats(), ctypes.c_int32(), ctypes.c_int32()
+        hist = np.zeros((STATS_LBINS, STATS_SBINS), dtype=np.uint32)
+        sumlen = np.zeros(STATS_LBINS, dtype=np.uint64)
+        tail = (ms, sh or 0, sd, ctypes.byref(s), hist.ctypes.data, sumlen.ctypes.data, ctypes.byref(m), ctypes.byref(r))
+        if isinstance(query_or_pssm, (str, bytes)):
+            q = query_or_pssm.encode() if isinstance(query_or_pssm, str) else query_or_pssm
+            _check(_shuffle_fns()[0](self.handle, q, len(q), *tail))
+        else:
+            from . import pssm as _pssm
+            p = _pssm.as_pssm(query_or_pssm)
+            _check(_shuffle_fns()[1](self.handle, p.ctypes.data, p.shape[0], *tail))
+        out = _stats_dict(s)
+        out.update(hist=hist, sumlen=sumlen, subjects=int(m.value), replicas=int(r.value), mode="shuffled")
+        return out
+
+    def _calibrate_for_submit(self, query_or_pssm):
+        """mode "shuffled": the calibration of a query about to be submitted, queued for its collect; under E-value ranking it
+        is also the fit the driver ranks that query by"""
+        if not (self.statistics and self.statistics_mode == "shuffled"):
+            return
+        cal = self.calibrate(query_or_pssm)
+        if self.ranking == "evalue":
+            c = _stats_struct(cal)
+            _check(_shuffle_fns()[2](self.handle, ctypes.byref(c)))
+        self._calibrations.append(cal)
+
+    def _checked(self, rc, submitted):
+        """_check for the calls that submit or collect a query: a failed call takes its query's calibration with it
+        (submitted: the newest one; else the oldest)"""
+        if rc != 0 and self._calibrations:
+            self._calibrations.pop(-1 if submitted else 0)
+        _check(rc)
 
     def last_statistics(self):
         """Fit and table of the query collected last (swdrv_last_statistics) -> the "stats" dict of its result."""
@@ -487,6 +567,11 @@ class Driver:
         if not self.statistics:
             return result
         st = self.last_statistics()
+        st["mode"] = "scan"
+        if self.statistics_mode == "shuffled":   # the calibration's fit and table, N from the scan's own table
+            cal = self._calibrations.pop(0)
+            cal["N"] = st["N"]
+            st = cal
         ids = result["ids"]
         lengths = np.array([self.reference_length(int(i)) for i in ids], dtype=np.int32)
         z = np.zeros(len(ids), dtype=np.float64)
@@ -646,13 +731,14 @@ class Driver:
     def scan(self, query_letters):
         if isinstance(query_letters, str):
             query_letters = query_letters.encode()
+        self._calibrate_for_submit(query_letters)
         cap = max(self.num_top, 1)
         scores = np.zeros(cap, dtype=np.int32)
         ids = np.zeros(cap, dtype=np.int64)
         nres, novf = ctypes.c_int(), ctypes.c_int()
         sec, gcups = ctypes.c_double(), ctypes.c_double()
-        _check(lib.swdrv_scan(self.handle, query_letters, len(query_letters), scores.ctypes.data, ids.ctypes.data, cap,
-                              ctypes.byref(nres), ctypes.byref(novf), ctypes.byref(sec), ctypes.byref(gcups)))
+        self._checked(lib.swdrv_scan(self.handle, query_letters, len(query_letters), scores.ctypes.data, ids.ctypes.data, cap,
+                                     ctypes.byref(nres), ctypes.byref(novf), ctypes.byref(sec), ctypes.byref(gcups)), True)
         n = nres.value
         return self._with_statistics({"scores": scores[:n].copy(), "ids": ids[:n].copy(), "num_overflows": novf.value,
                                       "num_rescored": int(lib.swdrv_last_rescored(self.handle)),
@@ -663,13 +749,14 @@ class Driver:
         subject code c, column 20 negative (cudasw4_amd.pssm).  Same result dict as scan()."""
         from . import pssm as _pssm
         m = _pssm.as_pssm(pssm)
+        self._calibrate_for_submit(m)
         cap = max(self.num_top, 1)
         scores = np.zeros(cap, dtype=np.int32)
         ids = np.zeros(cap, dtype=np.int64)
         nres, novf = ctypes.c_int(), ctypes.c_int()
         sec, gcups = ctypes.c_double(), ctypes.c_double()
-        _check(_pssm_fns()[0](self.handle, m.ctypes.data, m.shape[0], scores.ctypes.data, ids.ctypes.data, cap,
-                              ctypes.byref(nres), ctypes.byref(novf), ctypes.byref(sec), ctypes.byref(gcups)))
+        self._checked(_pssm_fns()[0](self.handle, m.ctypes.data, m.shape[0], scores.ctypes.data, ids.ctypes.data, cap,
+                                     ctypes.byref(nres), ctypes.byref(novf), ctypes.byref(sec), ctypes.byref(gcups)), True)
         n = nres.value
         return self._with_statistics({"scores": scores[:n].copy(), "ids": ids[:n].copy(), "num_overflows": novf.value,
                                       "num_rescored": int(lib.swdrv_last_rescored(self.handle)),
@@ -679,13 +766,15 @@ class Driver:
         """submit() with a PSSM query; collect() returns its results.  May be in flight together with a letter query."""
         from . import pssm as _pssm
         m = _pssm.as_pssm(pssm)
-        _check(_pssm_fns()[1](self.handle, m.ctypes.data, m.shape[0]))
+        self._calibrate_for_submit(m)
+        self._checked(_pssm_fns()[1](self.handle, m.ctypes.data, m.shape[0]), True)
 
     def submit(self, query_letters):
         """First half of scan(): enqueue the query on every GPU without waiting (at most two in flight)."""
         if isinstance(query_letters, str):
             query_letters = query_letters.encode()
-        _check(lib.swdrv_scan_submit(self.handle, query_letters, len(query_letters)))
+        self._calibrate_for_submit(query_letters)
+        self._checked(lib.swdrv_scan_submit(self.handle, query_letters, len(query_letters)), True)
 
     def collect(self):
         """Second half of scan(): the merged results of the oldest submitted query."""
@@ -694,8 +783,8 @@ class Driver:
         ids = np.zeros(cap, dtype=np.int64)
         nres, novf = ctypes.c_int(), ctypes.c_int()
         sec, gcups = ctypes.c_double(), ctypes.c_double()
-        _check(lib.swdrv_scan_collect(self.handle, scores.ctypes.data, ids.ctypes.data, cap, ctypes.byref(nres),
-                                      ctypes.byref(novf), ctypes.byref(sec), ctypes.byref(gcups)))
+        self._checked(lib.swdrv_scan_collect(self.handle, scores.ctypes.data, ids.ctypes.data, cap, ctypes.byref(nres),
+                                             ctypes.byref(novf), ctypes.byref(sec), ctypes.byref(gcups)), False)
         n = nres.value
         return self._with_statistics({"scores": scores[:n].copy(), "ids": ids[:n].copy(), "num_overflows": novf.value,
                                       "num_rescored": int(lib.swdrv_last_rescored(self.handle)),

@@ -42,3 +42,35 @@ def evalues(stats, scores, lengths):
     st = _driver._stats_struct(stats)
     _driver._check(_driver._stats_fns()[3](ctypes.byref(st), sc.ctypes.data, ln.ctypes.data, len(sc), z.ctypes.data, e.ctypes.data))
     return z, e
+
+
+# ---- statistics calibrated on shuffled subjects: the rules, without a GPU ----
+
+def shuffle_sample(n, max_subjects=_driver.SHUFFLE_DEFAULT_SUBJECTS):
+    """The sampled subject ids of a DB of n sequences (swdrv_shuffle_sample): ((2 j + 1) n) / (2 M) for j = 0 .. M - 1 with
+    M = min(n, max_subjects) -> int64 array, ascending and distinct."""
+    m = min(int(n), int(max_subjects))
+    out = np.zeros(max(m, 0), dtype=np.int64)
+    got = _driver._shuffle_fns()[3](int(n), int(max_subjects), out.ctypes.data)
+    if got < 0:
+        _driver._check(got)
+    return out[:got]
+
+
+def shuffle_replicas(subjects, shuffles=None):
+    """Replicas of a sample of `subjects` (swdrv_shuffle_replicas): `shuffles` (1 .. 64) when given, else
+    ceil(2000 / subjects) clamped to [1, 64]."""
+    if shuffles is not None and not 1 <= int(shuffles) <= _driver.SHUFFLE_MAX_REPLICAS:
+        raise ValueError("shuffles must lie in [1, %d]" % _driver.SHUFFLE_MAX_REPLICAS)
+    got = _driver._shuffle_fns()[4](int(subjects), int(shuffles or 0))
+    if got < 0:
+        _driver._check(got)
+    return int(got)
+
+
+def shuffle_permutation(length, seed, subject_id, replica=0):
+    """pi of a subject of true length `length` under (seed, subject_id, replica) (swdrv_shuffle_permutation): residue i of
+    the shuffled subject is residue pi[i] of the original -> int32 array."""
+    out = np.zeros(max(int(length), 0), dtype=np.int32)
+    _driver._check(_driver._shuffle_fns()[5](int(length), int(seed) & 0xFFFFFFFF, int(subject_id), int(replica), out.ctypes.data))
+    return out

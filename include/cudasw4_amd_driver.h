@@ -305,6 +305,37 @@ double swdrv_zscore_for_evalue(int64_t N, double X);
 int swdrv_rank_order(const swdrv_stats* stats, const int32_t* scores, const int32_t* lengths, const int64_t* ids, int n,
                      int32_t* out_order);
 
+/* Statistics calibrated on shuffled subjects (an extension; DESIGN.md §15, include/cudasw4_amd_shuffle.h): what FASTA /
+ * SSEARCH offer as -z 11 .. and PRSS does.  The fit above assumes that almost every subject is unrelated to the query; a
+ * database dominated by one family breaks that, and a database of fewer than 100 usable scores allows no fit at all.  Here the
+ * query is scored against a SAMPLE of the database whose subjects' residues are permuted on the device — length and
+ * composition kept, homology destroyed — and the same fit is made on those scores:
+ *   sample    M = min(n, max_subjects) subjects of the n the driver opened (whatever its shard or GPUs), ids
+ *             ((2 j + 1) n) / (2 M) for j = 0 .. M - 1: ascending, distinct, length-stratified in a sorted database
+ *   replicas  R = shuffles (1 .. 64), or with shuffles = 0 ceil(2000 / M) clamped to [1, 64]
+ *   shuffle   subject `id` (within the opened database, without id_base) in replica r by the permutation of
+ *             (seed, id, r, true length): include/cudasw4_amd_shuffle.h
+ *   scores    exact (SW_KIND_I32), with the driver's matrix — or the PSSM — and gap scores, on the driver's first GPU
+ *   table     the M R scores and true lengths through sw_score_histogram; the fit is swdrv_stats_from_histogram of it
+ * The calibrated statistics of a scan are that fit's a, b1, sd, rounds and status with N TAKEN FROM THE SCAN'S TABLE: the
+ * caller sets out->N (which these calls leave at M R) before swdrv_evalues.  The calibration depends on the query and the
+ * database only, so it may run before the scan is collected.  max_subjects >= 1.  out, hist (64 x 256), sumlen (64),
+ * subjects (M) and replicas (R) may each be NULL.  Where R replicas of the sample exceed max_temp_bytes they go through in
+ * chunks; the sample stays on the device between calls with the same (database, max_subjects, shuffles, seed). */
+int swdrv_calibrate_shuffled(swdrv* d, const char* query, int32_t qlen, int32_t max_subjects, int32_t shuffles, uint32_t seed,
+                             swdrv_stats* out, uint32_t* hist, uint64_t* sumlen, int32_t* subjects, int32_t* replicas);
+int swdrv_calibrate_shuffled_pssm(swdrv* d, const int8_t* pssm, int32_t qlen, int32_t max_subjects, int32_t shuffles, uint32_t seed,
+                                  swdrv_stats* out, uint32_t* hist, uint64_t* sumlen, int32_t* subjects, int32_t* replicas);
+/* Under SWDRV_RANK_EVALUE: the fit of the NEXT collected query — its status, a, b1 and sd, with N from that query's own
+ * table — in place of the fit of the table (fit == NULL: back to that).  Set while nothing is in flight; the collect clears it. */
+int swdrv_set_rank_fit(swdrv* d, const swdrv_stats* fit);
+/* The rules alone (no GPU needed).  swdrv_shuffle_sample: out_ids (may be NULL) receives the M ids, returns M;
+ * swdrv_shuffle_replicas: returns R; swdrv_shuffle_permutation: out[i] (L entries) = the position residue i of the shuffled
+ * subject is taken from.  -1 on error. */
+int swdrv_shuffle_sample(int64_t n, int64_t max_subjects, int64_t* out_ids);
+int swdrv_shuffle_replicas(int64_t M, int32_t shuffles);
+int swdrv_shuffle_permutation(int32_t L, uint32_t seed, int64_t id, int32_t replica, int32_t* out);
+
 /* ---- input helpers (no GPU needed): what `align` does to its inputs before the scan ---- */
 
 /* ConvertAA_20 (convert.cuh:6-34): letters -> codes 0..20 */
