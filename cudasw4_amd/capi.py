@@ -46,6 +46,8 @@ HSPS_EXPORTS = ["sw_align_hsps", "sw_align_hsps_pssm"]
 MAX_HSPS = 16
 # ... and include/cudasw4_amd_shuffle.h (statistics calibrated on shuffled subjects: replicas of a block, every subject permuted)
 SHUFFLE_EXPORTS = ["sw_shuffle_subjects"]
+# ... and include/cudasw4_amd_mask.h (low-complexity masking of the subjects on the device)
+MASK_EXPORTS = ["sw_mask_subjects", "sw_mask_subjects_phases"]
 
 
 # sw_align_hits (include/cudasw4_amd.h): result records, statuses, flags, CIGAR op codes
@@ -84,6 +86,10 @@ class _AlignArgs(ctypes.Structure):
 
 class _HspArgs(ctypes.Structure):
     _fields_ = [("max_hsps", ctypes.c_int32), ("min_score", ctypes.c_int32)]
+
+
+class _MaskParams(ctypes.Structure):
+    _fields_ = [("window", ctypes.c_int32), ("trigger_sum", ctypes.c_int32), ("extend_sum", ctypes.c_int32)]
 
 
 class SwError(RuntimeError):
@@ -157,6 +163,9 @@ def _load():
         L.sw_gather_hits.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, vp, vp]
     if hasattr(L, "sw_shuffle_subjects"):
         L.sw_shuffle_subjects.argtypes = [vp, vp, vp, vp, vp, i32, ctypes.c_uint32, i32, i32, vp, sz, vp]
+    if hasattr(L, "sw_mask_subjects"):
+        L.sw_mask_subjects.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(_MaskParams), vp, vp, sz, ctypes.POINTER(sz), vp, vp]
+        L.sw_mask_subjects_phases.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(_MaskParams), vp, vp, sz, vp, vp, ctypes.POINTER(vp)]
     return L
 
 
@@ -441,6 +450,40 @@ def shuffle_subjects(ctx, chars, offsets, lengths, n, seed, out, replica_stride,
     check(lib.sw_shuffle_subjects(ctx.handle if ctx is not None else None, chars or None, offsets or None, lengths or None,
                                   keys or None, n, seed & 0xFFFFFFFF, first_replica, replicas, out or None, replica_stride,
                                   stream or None))
+
+
+def mask_subjects(ctx, chars, offsets, lengths, n, window, trigger_sum, extend_sum, out, temp=0, temp_bytes=0, counts=0, stream=0):
+    """sw_mask_subjects (include/cudasw4_amd_mask.h): the n subjects (chars, offsets, lengths: dbdata layout) with their
+    low-complexity segments replaced by code 20, to out (== chars: in place; otherwise the whole block is written).  temp:
+    scratch of temp_bytes bytes (mask_subjects_temp_bytes holds all n subjects in one go; with less the call works through
+    ranges of whole subjects); counts (uint64[2]) is INCREASED by the covered positions and the subjects with a segment.
+    Every buffer is a device pointer as an integer.  Asynchronous on `stream` behind a read-back of the block's two ends."""
+    if not hasattr(lib, "sw_mask_subjects"):
+        raise SwError(-1, "this build of libcudasw4_amd.so has no sw_mask_subjects")
+    p = _MaskParams(window, trigger_sum, extend_sum)
+    check(lib.sw_mask_subjects(ctx.handle if ctx is not None else None, chars or None, offsets or None, lengths or None, n,
+                               ctypes.byref(p), out or None, temp or None, temp_bytes, None, counts or None, stream or None))
+
+
+def mask_subjects_phases(ctx, chars, offsets, lengths, n, window, trigger_sum, extend_sum, out, temp, temp_bytes, events, counts=0,
+                         stream=0):
+    """sw_mask_subjects_phases: mask_subjects with four HIP events (handles as integers) recorded before the flags, the resolve
+    and the apply launch and behind the last one; the scratch must take the block in one go."""
+    p = _MaskParams(window, trigger_sum, extend_sum)
+    ev = (ctypes.c_void_p * 4)(*[int(e) for e in events])
+    check(lib.sw_mask_subjects_phases(ctx.handle if ctx is not None else None, chars or None, offsets or None, lengths or None, n,
+                                      ctypes.byref(p), out or None, temp or None, temp_bytes, counts or None, stream or None, ev))
+
+
+def mask_subjects_temp_bytes(ctx, offsets, n, window=12, trigger_sum=20705, extend_sum=17019, stream=0):
+    """the scratch sw_mask_subjects needs to take the n subjects behind `offsets` (device) in one go; nothing is launched"""
+    if not hasattr(lib, "sw_mask_subjects"):
+        raise SwError(-1, "this build of libcudasw4_amd.so has no sw_mask_subjects")
+    p = _MaskParams(window, trigger_sum, extend_sum)
+    need = ctypes.c_size_t(0)
+    check(lib.sw_mask_subjects(ctx.handle if ctx is not None else None, None, offsets or None, None, n, ctypes.byref(p), None,
+                               None, 0, ctypes.byref(need), None, stream or None))
+    return int(need.value)
 
 
 def topk_temp_bytes(n, k):

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cctype>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <deque>
@@ -214,6 +215,14 @@ const EvalueReport* evalueReport(const ProgramOptions& o, const ScanResult& r, E
 
 // --rankBy evalue --maxEvalue X --verbose: how many subjects of the whole DB lie at or under the threshold, and how many of
 // them the --top list reports
+// --verbose with --maskSubjects: what the pass over the DB behind the query collected last masked
+void reportMasking(const ProgramOptions& o, const SearchDriver& d) {
+    if (!o.verbose || !d.masksSubjects()) return;
+    const SearchDriver::MaskingCounts c = d.maskingCounts();
+    std::cout << "subject masking: window " << d.maskParams().window << " trigger " << o.maskTrigger << " extend " << o.maskExtend << ": "
+              << c.positions << " of " << c.residuesSeen << " residues in " << c.subjects << " of " << d.numSequences() << " subjects\n";
+}
+
 void reportSignificant(const ProgramOptions& o, const ScanResult& r, const SearchDriver& d, const EvalueReport* ev) {
     if (!o.verbose || !o.rankByEvalue() || !o.haveMaxEvalue || !(o.maxEvalue > 0) || !ev) return;
     if (r.significant < 0) { std::cout << "significant: no fit\n"; return; }
@@ -327,6 +336,7 @@ void processQueryFile(const std::string& file, const ProgramOptions& o, SearchDr
         std::cout.flush();
         ScanResult r = driver.collect();
         reportScan(o, r);
+        reportMasking(o, driver);
         IterationResult rounds;
         if (iteration) rounds = runIterations(o, driver, *iteration, q.num, q.sequence, nullptr, r);
         if (o.numTopOutputs > 0 || interactive) {
@@ -384,6 +394,7 @@ void processPssmQuery(const PssmQuery& q, const ProgramOptions& o, SearchDriver&
     submit_pssm(driver, q.scores.data(), q.length());
     ScanResult r = driver.collect();
     reportScan(o, r);
+    reportMasking(o, driver);
     IterationResult rounds;
     if (iteration) rounds = runIterations(o, driver, *iteration, 0, q.consensus, q.scores.data(), r);
     if (o.numTopOutputs > 0) {
@@ -456,6 +467,22 @@ int main(int argc, char** argv) {
         if (!(options.pseudocount > 0)) throw std::runtime_error("--pseudocount must be positive");
         if (options.buildsPssm() && options.interactive) throw std::runtime_error("--iterations / --outPssm cannot be combined with --interactive");
         if (options.buildsPssm() && options.numTopOutputs < 1) throw std::runtime_error("--iterations / --outPssm need --top of at least 1: the PSSM is built from the reported results");
+        if ((options.haveMaskWindow || options.haveMaskTrigger || options.haveMaskExtend) && !options.maskSubjects)
+            throw std::runtime_error("--maskWindow / --maskTrigger / --maskExtend need --maskSubjects: they say how the subjects are masked");
+        MaskParams maskParams;
+        if (options.maskSubjects) {
+            auto number = [](const std::string& text, const char* flag, bool integer) {
+                char* end = nullptr;
+                const double v = integer ? double(std::strtol(text.c_str(), &end, 10)) : std::strtod(text.c_str(), &end);
+                if (text.empty() || *end != 0 || !std::isfinite(v)) throw std::runtime_error(std::string(flag) + " needs a number, not '" + text + "'");
+                return v;
+            };
+            const double window = number(options.maskWindow, "--maskWindow", true);
+            const double trigger = number(options.maskTrigger, "--maskTrigger", false), extend = number(options.maskExtend, "--maskExtend", false);
+            if (window < 4 || window > 32) throw std::runtime_error("--maskWindow must lie in 4 .. 32");
+            if (trigger > extend) throw std::runtime_error("--maskTrigger must not be above --maskExtend: a segment starts at a window of at most K1 bits and extends over windows of at most K2");
+            maskParams = mask_params_from_bits(int(window), trigger, extend);
+        }
         std::vector<PssmQuery> pssmQueries;
         for (const auto& file : options.pssmFiles) pssmQueries.push_back(read_ascii_pssm(file));
         std::vector<int> deviceIds;
@@ -482,6 +509,7 @@ int main(int argc, char** argv) {
 
         SearchDriver driver(deviceIds, options.numTopOutputs, options.matrix, options.kernels, options.memory, options.verbose,
                             options.effectiveGop(), options.effectiveGex());
+        if (options.maskSubjects) enable_subject_masking(driver, &maskParams);
         if (!options.usePseudoDB) {
             if (options.verbose) std::cout << "Reading Database: \n";
             Stopwatch t;
@@ -549,6 +577,7 @@ int main(int argc, char** argv) {
                         std::cout.flush();
                         ScanResult r = driver.scan(sequence.data(), int32_t(sequence.size()));
                         reportScan(options, r);
+                        reportMasking(options, driver);
                         std::vector<HitAlignment> alignments;
                         HspLists lists;
                         if (aligner && options.reportHsps()) lists = alignHsps(options, *aligner, sequence, nullptr, r, alignments);

@@ -46,6 +46,10 @@ void printOptions(const ProgramOptions& o) {
     if (o.haveShuffles) std::cout << "shuffles: " << o.shuffles << "\n";
     if (o.haveShuffleSubjects) std::cout << "shuffleSubjects: " << o.shuffleSubjects << "\n";
     if (o.haveShuffleSeed) std::cout << "shuffleSeed: " << o.shuffleSeed << "\n";
+    if (o.maskSubjects) std::cout << "maskSubjects: 1\n";
+    if (o.haveMaskWindow) std::cout << "maskWindow: " << o.maskWindow << "\n";
+    if (o.haveMaskTrigger) std::cout << "maskTrigger: " << o.maskTrigger << "\n";
+    if (o.haveMaskExtend) std::cout << "maskExtend: " << o.maskExtend << "\n";
     if (!o.outPssm.empty()) std::cout << "outPssm: " << o.outPssm << "\n";
     std::cout << "blosum: " << substitution_matrix(o.matrix).name << "\n";
     std::cout << "singlePassType: " << to_string(o.kernels.singlePassType) << "\n";
@@ -97,6 +101,10 @@ bool parseArgs(int argc, char** argv, ProgramOptions& o) {
         else if (arg == "--shuffles") { o.shuffles = std::atoll(value(i).c_str()); o.haveShuffles = true; }
         else if (arg == "--shuffleSubjects") { o.shuffleSubjects = std::atoll(value(i).c_str()); o.haveShuffleSubjects = true; }
         else if (arg == "--shuffleSeed") { o.shuffleSeed = std::strtoull(value(i).c_str(), nullptr, 10); o.haveShuffleSeed = true; }
+        else if (arg == "--maskSubjects") o.maskSubjects = true;
+        else if (arg == "--maskWindow") { o.maskWindow = value(i); o.haveMaskWindow = true; }
+        else if (arg == "--maskTrigger") { o.maskTrigger = value(i); o.haveMaskTrigger = true; }
+        else if (arg == "--maskExtend") { o.maskExtend = value(i); o.haveMaskExtend = true; }
         else if (arg == "--pseudocount") o.pseudocount = std::atof(value(i).c_str());
         else if (arg == "--outPssm") o.outPssm = value(i);
         else if (arg == "--printLengthPartitions") o.printLengthPartitions = true;
@@ -191,6 +199,13 @@ void printHelp(char** argv) {
     std::cout << "      --shuffles R : With --statistics shuffled: every subject of the sample is permuted R times (1 .. 64). Default: as many as\n"
                  "        bring 2000 scores, 1 .. 64.\n";
     std::cout << "      --shuffleSeed S : With --statistics shuffled: seed of the permutations. Default: 1.\n\n";
+    std::cout << "   Subject masking\n";
+    std::cout << "      --maskSubjects : Mask low-complexity segments of the subjects (poly-Q, S/G/A-rich linkers, short repeats) on the GPU before\n"
+                 "        they are scanned: the trigger and extension stages of SEG on a fixed window. A masked residue scores like X; alignments\n"
+                 "        and PSSMs see the masked subject. With --verbose, one line per query with the residues and subjects masked.\n";
+    std::cout << "      --maskWindow W : With --maskSubjects: the window, 4 .. 32. Default: 12.\n";
+    std::cout << "      --maskTrigger K1 : With --maskSubjects: a window of at most K1 bits of entropy starts a segment. Default: 1.9.\n";
+    std::cout << "      --maskExtend K2 : With --maskSubjects: the segment extends over adjacent windows of at most K2 bits, K1 <= K2. Default: 2.2.\n\n";
     std::cout << "   Memory\n";
     std::cout << "      --maxGpuMem val : Try not to use more than val bytes of gpu memory per gpu. Uses all available gpu memory by default\n";
     std::cout << "      --maxTempBytes val : Size of temp storage in GPU memory. Can use suffix K,M,G. Default val = " << d.memory.maxTempBytes << "\n";

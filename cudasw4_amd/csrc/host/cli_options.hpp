@@ -66,6 +66,12 @@ struct ProgramOptions {
     bool shuffledStatistics() const { return statistics == "shuffled"; }
     bool reportEvalues() const { return evalues || haveMaxEvalue || rankByEvalue() || shuffledStatistics(); }
     bool wantStatistics() const { return reportEvalues() || haveInclusionEvalue; }
+    // --maskSubjects (subject_mask.hpp; an extension): low-complexity segments of the subjects are masked on the
+    // GPU before anything scans them; --maskWindow W, --maskTrigger K1 and --maskExtend K2 (entropies in bits) replace the
+    // defaults.  The values are kept as given and checked in main, before any device is opened.
+    bool maskSubjects = false;
+    bool haveMaskWindow = false, haveMaskTrigger = false, haveMaskExtend = false;
+    std::string maskWindow = "12", maskTrigger = "1.9", maskExtend = "2.2";
     bool prefetchDBFile = false;
     int numTopOutputs = 10;
     int gop = -11;

@@ -212,6 +212,8 @@ std::vector<HitAlignment> HitAligner::run(const int8_t* codes, const int8_t* pss
         const size_t padded = (s.size() + 3) / 4 * 4;
         chars.resize(size_t(offsets[i]) + padded, kOtherCode);
         for (size_t k = 0; k < s.size(); k++) chars[size_t(offsets[i]) + k] = encode_residue(s[k]);
+        // what the scan scored is the masked subject: the score check below holds the two statements together
+        if (d_.masksSubjects()) mask_subject(chars.data() + offsets[i], lengths[i], d_.maskParams(), chars.data() + offsets[i]);
         offsets[i + 1] = offsets[i] + padded;
         for (size_t k = 0; k < H; k++) cigarOffsets[i * H + k + 1] = cigarOffsets[i * H + k] + qlen + lengths[i];
         traceBytes = std::max(traceBytes, trace_bytes_for(size_t(qlen), s.size()));

@@ -200,6 +200,14 @@ struct SearchDriver::Gpu {
     // chars arrive: the cached part after its upload, every streamed batch the first time it is scanned
     std::vector<bool> batchChecked;
     bool badCodes = false;
+    // subject masking (SearchDriver::setSubjectMasking): counts on the device ([0 .. 1]: the upload of the resident / cached
+    // part, [2 .. 3]: the streamed batches of the scan being enqueued), the host's copies of both halves, the true residues
+    // each half passed, and one scratch per work stream for the batches of a streamed scan
+    unsigned long long* d_maskCounts = nullptr;
+    uint64_t maskUpload[2] = {0, 0}, maskStreamed[2] = {0, 0};
+    uint64_t maskUploadResidues = 0, maskStreamedResidues = 0;
+    void* d_maskTemp[2] = {nullptr, nullptr};
+    size_t maskTempCap = 0;
     // streaming: three device staging buffers fed from the (registered) DB mapping, or through pinned host buffers
     std::vector<Batch> batches;
     // Two batches compute at a time (one per work stream) while a third is being copied in: three buffers
@@ -342,6 +350,8 @@ struct SearchDriver::Gpu {
         ScoreTable* d_table = nullptr;
         ScoreTable* h_table = nullptr;
         bool tapped = false;
+        unsigned long long* h_mask = nullptr;   // subject masking: the counts of the scan's streamed batches
+        bool masked = false;
     };
     ResultSlot res[SearchDriver::kMaxInFlight];
     // E-value ranking (SearchDriver::setRanking): keys and identity positions of the shard, the top-K's choice among them
@@ -497,6 +507,7 @@ SearchDriver::~SearchDriver() {
                 if (g.auxDone[i][a]) (void)hipEventDestroy(g.auxDone[i][a]);
         }
         (void)hipHostFree(g.h_pad);
+        (void)hipFree(g.d_maskCounts); (void)hipFree(g.d_maskTemp[0]); (void)hipFree(g.d_maskTemp[1]);
         if (g.laneSwapped) g.swapLane();
         if (g.eng) sw_batch_destroy(g.eng);
         if (g.lane1.eng) sw_batch_destroy(g.lane1.eng);
@@ -512,6 +523,7 @@ SearchDriver::~SearchDriver() {
             if (r.done) (void)hipEventDestroy(r.done);
             (void)hipHostFree(r.h_topS); (void)hipHostFree(r.h_topI); (void)hipHostFree(r.h_ovf);
             (void)hipFree(r.d_table); (void)hipHostFree(r.h_table);
+            (void)hipHostFree(r.h_mask);
         }
         (void)hipFree(g.rank.d_keys); (void)hipFree(g.rank.d_pos); (void)hipFree(g.rank.d_topKey); (void)hipFree(g.rank.d_topPos);
         (void)hipFree(g.rank.d_count); (void)hipHostFree(g.rank.h_count);
@@ -558,6 +570,24 @@ void SearchDriver::setShard(int rank, int world, int64_t idBase) {
     shardRank_ = rank;
     shardWorld_ = world;
     idBase_ = idBase;
+}
+
+void SearchDriver::setSubjectMasking(SubjectMaskFn mask, const MaskParams& params) {
+    if (db_) throw std::runtime_error("setSubjectMasking after the database was set: the subjects on the GPUs are what the scans read");
+    if (mask && (params.window < 4 || params.window > 32 || params.extendSum < 1 || params.triggerSum < params.extendSum))
+        throw std::runtime_error("subject masking: window 4 .. 32 and 1 <= extend sum <= trigger sum are required");
+    maskFn_ = mask;
+    maskParams_ = params;
+}
+
+SearchDriver::MaskingCounts SearchDriver::maskingCounts() const {
+    MaskingCounts c;
+    for (const auto& gp : gpus_) {
+        c.positions += gp->maskUpload[0] + gp->maskStreamed[0];
+        c.subjects += gp->maskUpload[1] + gp->maskStreamed[1];
+        c.residuesSeen += gp->maskUploadResidues + gp->maskStreamedResidues;
+    }
+    return c;
 }
 
 // fn(src, bytes, dstOffset) for every contiguous piece of the DB's chars that the shard-local subjects [lbegin, lend)
@@ -607,6 +637,8 @@ void SearchDriver::setDatabase(std::shared_ptr<Database> db) {
         g.numLocal = g.localBegin[kNumLengthPartitions];
         g.cacheFilled = false;
         g.badCodes = false;
+        g.maskUpload[0] = g.maskUpload[1] = g.maskStreamed[0] = g.maskStreamed[1] = 0;
+        g.maskUploadResidues = g.maskStreamedResidues = 0;
         g.resPrefix.clear();
         // shard-local byte offsets (the pieces of the partitions follow each other) and true residues
         g.localOffsets.assign(g.numLocal + 1, 0);
@@ -838,6 +870,36 @@ void SearchDriver::uploadShard(Gpu& g) {
         HIPCHECK(hipStreamSynchronize(g.stream));
         if (bad) { g.badCodes = true; throw DbLoadError("DB chars hold letter codes outside 0..20 (not a cudasw4 DB, or corrupt)"); }
     }
+    if (maskFn_) {
+        // once per upload, in place, in ranges of whole subjects that fit a scratch within --maxTempBytes (no scan is in
+        // flight on this GPU during an upload: the scratch lives for the call)
+        TraceRange traceMask("mask %ld resident subjects", long(g.numLocal - g.cacheBegin));
+        const int32_t n = int32_t(g.numLocal - g.cacheBegin);
+        size_t need = 0;
+        if (maskFn_(g.ctx, g.d_chars, g.d_offsets + g.cacheBegin, g.d_lengths + g.cacheBegin, n, maskParams_, nullptr, 0, &need, nullptr, g.stream) != 0)
+            throw std::runtime_error(std::string("subject masking: ") + sw_last_error());
+        const size_t bytes = std::max<size_t>(std::min(need, std::min(memory_.maxTempBytes, g.tempCap)), 8);
+        if (!g.d_maskCounts) HIPCHECK(hipMalloc(&g.d_maskCounts, 4 * sizeof(unsigned long long)));
+        void* temp = nullptr;
+        HIPCHECK(hipMalloc(&temp, bytes));
+        HIPCHECK(hipMemsetAsync(g.d_maskCounts, 0, 2 * sizeof(unsigned long long), g.stream));
+        const int rc = maskFn_(g.ctx, g.d_chars, g.d_offsets + g.cacheBegin, g.d_lengths + g.cacheBegin, n, maskParams_, temp, bytes, nullptr,
+                               g.d_maskCounts, g.stream);
+        unsigned long long got[2] = {0, 0};
+        if (rc == 0) (void)hipMemcpyAsync(got, g.d_maskCounts, sizeof(got), hipMemcpyDeviceToHost, g.stream);
+        const hipError_t se = hipStreamSynchronize(g.stream);
+        (void)hipFree(temp);
+        if (rc != 0) throw std::runtime_error(std::string("subject masking: ") + sw_last_error());
+        HIPCHECK(se);
+        g.maskUpload[0] = got[0];
+        g.maskUpload[1] = got[1];
+        uint64_t residues = 0;
+        for (int p = 0; p < kNumLengthPartitions; p++) {
+            const size_t lb = std::max(g.cacheBegin, g.localBegin[p]), le = g.localBegin[p + 1];
+            for (size_t i = lb; i < le; i++) residues += uint64_t(db_->length(g.ranges[p].begin + (i - g.localBegin[p])));
+        }
+        g.maskUploadResidues = residues;
+    }
     HIPCHECK(hipStreamSynchronize(g.stream));
     g.cacheFilled = true;
 }
@@ -1007,6 +1069,19 @@ void SearchDriver::scanStreamed(Gpu& g) {
         }
         g.pinnedCap = maxBytes + 64;
     }
+    if (maskFn_) {
+        // a scratch per work stream that takes the largest batch in one go where that fits --maxTempBytes (24 bytes per 64
+        // of the batch); with less the library works through ranges of whole subjects
+        const size_t want = std::max<size_t>(std::min(size_t((maxBytes + 63) / 64 * 24), std::min(memory_.maxTempBytes, g.tempCap)), 8);
+        if (want > g.maskTempCap) {
+            for (void*& t : g.d_maskTemp) {
+                (void)hipFree(t);
+                t = nullptr;
+                HIPCHECK(hipMalloc(&t, want));
+            }
+            g.maskTempCap = want;
+        }
+    }
     while (g.batchEv.size() < 2 * nb) {
         hipEvent_t e;
         HIPCHECK(hipEventCreate(&e));
@@ -1084,6 +1159,14 @@ void SearchDriver::scanStreamed(Gpu& g) {
             // the flag is the word behind this scan's overflow counters (enqueueOnGpu zeroes and copies it back)
             SWCHECK(sw_check_letter_codes(g.ctx, dst, b.bytes, g.d_ovfCount + (1 + nb) * size_t(SW_BATCH_COUNTERS), work));
             g.batchChecked[nb - 1 - k] = true;
+        }
+        if (maskFn_) {
+            // once per copy of a batch, on the work stream that scans it (nothing goes on the copy stream: see the padding
+            // DMA above).  The batch staged ahead by the scan before is masked here, by the scan that uses it.
+            TraceRange traceMask("mask batch %d", int(k + 1));
+            if (maskFn_(g.ctx, dst, g.d_offsets + b.lbegin, g.d_lengths + b.lbegin, int32_t(b.lend - b.lbegin), maskParams_,
+                        g.d_maskTemp[second ? 1 : 0], g.maskTempCap, nullptr, g.d_maskCounts + 2, work) != 0)
+                throw std::runtime_error(std::string("subject masking: ") + sw_last_error());
         }
         HIPCHECK(hipEventRecord(g.batchEv[2 * k], work));
         enqueue_batch(g, dst, b.lbegin, b.lend, *db_, kernels_, memory_, gop_, gex_, recordEvents_, k + 1, slot, second);
@@ -1320,6 +1403,12 @@ void SearchDriver::enqueueOnGpu(Gpu& g, int32_t queryLength, int k, int slot, bo
         }
         ensure_ovf_slots(rs.h_ovf, rs.ovfCap, ncounters + 1);
         HIPCHECK(hipMemsetAsync(g.d_ovfCount, 0, (ncounters + 1) * sizeof(int32_t), g.stream));
+        rs.masked = maskFn_ && !g.batches.empty();
+        if (rs.masked) {
+            if (!g.d_maskCounts) HIPCHECK(hipMalloc(&g.d_maskCounts, 4 * sizeof(unsigned long long)));
+            if (!rs.h_mask) HIPCHECK(hipHostMalloc(&rs.h_mask, 2 * sizeof(unsigned long long)));
+            HIPCHECK(hipMemsetAsync(g.d_maskCounts + 2, 0, 2 * sizeof(unsigned long long), g.stream));
+        }
         HIPCHECK(hipEventRecord(g.scanStartEv, g.stream));
         // the cached part first (the longest subjects: one set of launches over everything that is resident), then the
         // streamed batches — whose first copies run while the cached part computes
@@ -1331,6 +1420,7 @@ void SearchDriver::enqueueOnGpu(Gpu& g, int32_t queryLength, int k, int slot, bo
         }
         if (!g.batches.empty()) scanStreamed(g);
         join_aux(g);
+        if (rs.masked) HIPCHECK(hipMemcpyAsync(rs.h_mask, g.d_maskCounts + 2, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, g.stream));
         // the score tap: every launch that writes scores — streamed batches, windows, re-score, pipelines — has joined
         if (scoreTap_) {
             if (!rs.d_table) HIPCHECK(hipMalloc(&rs.d_table, sizeof(ScoreTable)));
@@ -1466,6 +1556,11 @@ void SearchDriver::finishOnGpu(Gpu& g, int slot, int32_t qlen) {
         throw std::runtime_error("scan failed: " + std::to_string(failed) +
                                  " pipeline stage(s) of a long subject gave up waiting for their neighbour (sw_scan_rows_pipelined)");
     g.lastTop = rs.top;
+    if (rs.masked) {
+        g.maskStreamed[0] = rs.h_mask[0];
+        g.maskStreamed[1] = rs.h_mask[1];
+        g.maskStreamedResidues = g.localResidues - g.maskUploadResidues;
+    }
     if (rs.tapped) g.lastTable = rs.h_table;
     // how much recent scans re-scored arms and sizes the re-score service of the lane's engine
     if (sw_batch* e = rs.lane == 1 ? (g.laneSwapped ? g.eng : g.lane1.eng) : (g.laneSwapped ? g.lane1.eng : g.eng)) SWCHECK(sw_batch_feedback(e, int32_t(std::max<int64_t>(0, int64_t(g.lastRescored) - dirty))));

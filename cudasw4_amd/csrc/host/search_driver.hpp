@@ -20,6 +20,7 @@
 
 #include "db_format.hpp"
 #include "sequence_codec.hpp"
+#include "subject_mask.hpp"
 
 struct sw_ctx;
 
@@ -206,6 +207,22 @@ public:
     // of every length partition (partitionDBAmongstGpus over all GPUs of the job, cudasw4.cuh:928-1004); ids stay
     // global.  Call before setDatabase.  idBase is added to every reported id (weak-scaling replicas).
     void setShard(int rank, int world, int64_t idBase = 0);
+    // Low-complexity masking of the subjects: with `mask` set, every copy of subject chars that reaches a GPU is
+    // masked in place on the device before anything scans it — the resident / cached part once behind its upload, every
+    // streamed batch once behind each of its copies — and hit alignment and the shuffled calibration mask the subjects they
+    // gather on the host (swh::mask_subject).  Like QueryInstallFn the function lives in the caller's translation unit
+    // (subject_mask.cpp: sw_mask_subjects, in place), with temp == nullptr it only reports the scratch the block needs.
+    // Call before setDatabase, like setShard: afterwards it throws.  nullptr: off — nothing is allocated or launched.
+    using SubjectMaskFn = int (*)(sw_ctx* ctx, int8_t* chars, const uint64_t* offsets, const int32_t* lengths, int32_t n,
+                                  const MaskParams& params, void* temp, size_t tempBytes, size_t* tempBytesNeeded,
+                                  unsigned long long* counts, void* stream);
+    void setSubjectMasking(SubjectMaskFn mask, const MaskParams& params);
+    bool masksSubjects() const { return maskFn_ != nullptr; }
+    const MaskParams& maskParams() const { return maskParams_; }
+    // the most recent complete pass over the DB, summed over the GPUs: the resident part's upload plus the streamed batches of
+    // the scan collected last; zeros before any pass
+    struct MaskingCounts { uint64_t positions = 0, subjects = 0, residuesSeen = 0; };
+    MaskingCounts maskingCounts() const;
     void setDatabase(std::shared_ptr<Database> db);  // cudasw4.cuh:552-568
     void prefetchDBToGpus();                         // cudasw4.cuh:651-696 (--uploadFull)
     void setNumTop(int k) { numTop_ = k; }           // cudasw4.cuh:574-587
@@ -345,6 +362,8 @@ private:
     std::vector<int8_t> encodedQuery_;
     QueryInstallFn queryInstall_ = nullptr;   // submitWith: what installs encodedQuery_ (nullptr: sw_set_query)
     ScoreTapFn scoreTap_ = nullptr;
+    SubjectMaskFn maskFn_ = nullptr;
+    MaskParams maskParams_;
     const RankHooks* rankHooks_ = nullptr;
     double rankMaxEvalue_ = 0;
     RankFit nextRankFit_;             // setRankFit: the fit of the next collected query

@@ -114,6 +114,8 @@ ShuffleCalibrator::ShuffleCalibrator(const SearchDriver& driver, int32_t maxSubj
         const size_t padded = (s.size() + 3) / 4 * 4;
         chars.resize(size_t(offsets[j]) + padded, kOtherCode);
         for (size_t k = 0; k < s.size(); k++) chars[size_t(offsets[j]) + k] = encode_residue(s[k]);
+        // the scans the fit stands for read masked subjects: so does the calibration
+        if (driver.masksSubjects()) mask_subject(chars.data() + offsets[j], lengths_[j], driver.maskParams(), chars.data() + offsets[j]);
         offsets[j + 1] = offsets[j] + padded;
     }
     blockBytes_ = chars.size();

@@ -28,7 +28,8 @@ EXPORTS = ["swdrv_last_error", "swdrv_create", "swdrv_destroy", "swdrv_open_db",
            "swdrv_set_statistics", "swdrv_last_statistics", "swdrv_stats_from_histogram", "swdrv_evalues", "swdrv_length_bin",
            "swdrv_set_ranking", "swdrv_last_ranking", "swdrv_zscore_for_evalue", "swdrv_rank_order",
            "swdrv_calibrate_shuffled", "swdrv_calibrate_shuffled_pssm", "swdrv_set_rank_fit", "swdrv_shuffle_sample",
-           "swdrv_shuffle_replicas", "swdrv_shuffle_permutation"]
+           "swdrv_shuffle_replicas", "swdrv_shuffle_permutation",
+           "swdrv_set_subject_masking", "swdrv_masking_counts", "swdrv_mask_threshold", "swdrv_mask_subject"]
 
 
 class DriverError(RuntimeError):
@@ -256,6 +257,22 @@ def _shuffle_fns():
         reps.argtypes = [i64, i32]
         perm.argtypes = [i32, u32, i64, i32, vp]
     return cal, calp, setfit, sample, reps, perm
+
+
+def _mask_fns():
+    """swdrv_set_subject_masking / swdrv_masking_counts / swdrv_mask_threshold / swdrv_mask_subject, bound on first use (not in
+    every build of this C ABI)"""
+    seton, counts, thr, one = (lib.swdrv_set_subject_masking, lib.swdrv_masking_counts, lib.swdrv_mask_threshold,
+                               lib.swdrv_mask_subject)
+    if seton.argtypes is None:
+        vp, i32, u64p = ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64)
+        seton.argtypes = [vp, ctypes.c_int, i32, ctypes.c_double, ctypes.c_double]
+        counts.argtypes = [vp, u64p, u64p, u64p]
+        thr.argtypes = [i32, ctypes.c_double]
+        thr.restype = i32
+        one.argtypes = [vp, i32, i32, i32, i32, vp]
+        one.restype = ctypes.c_int64
+    return seton, counts, thr, one
 
 
 RANK_SCORE, RANK_EVALUE = 0, 1
@@ -611,6 +628,19 @@ class Driver:
     def set_shard(self, rank, world, id_base=0):
         """One process per GPU: take shard `rank` of `world` (call before loading the DB)."""
         _check(lib.swdrv_set_shard(self.handle, rank, world, id_base))
+
+    def set_subject_masking(self, on=True, window=12, trigger_bits=1.9, extend_bits=2.2):
+        """Low-complexity masking of the subjects on the GPU (cudasw4_amd.mask states the rule): every copy of
+        subject chars that reaches a GPU is masked before it is scanned, and align_hits / align_hsps / build_pssm / calibrate
+        see the same masked subjects.  Call before loading the DB, like set_shard: afterwards it raises."""
+        _check(_mask_fns()[0](self.handle, int(bool(on)), int(window), float(trigger_bits), float(extend_bits)))
+
+    def masking_counts(self):
+        """The most recent complete pass over the DB, summed over the GPUs (swdrv_masking_counts) -> dict(positions, subjects,
+        residues_seen): the resident part's upload plus the streamed batches of the query collected last."""
+        p, sj, r = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        _check(_mask_fns()[1](self.handle, ctypes.byref(p), ctypes.byref(sj), ctypes.byref(r)))
+        return {"positions": int(p.value), "subjects": int(sj.value), "residues_seen": int(r.value)}
 
     def upload(self):
         _check(lib.swdrv_upload(self.handle))

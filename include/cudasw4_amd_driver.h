@@ -336,6 +336,23 @@ int swdrv_shuffle_sample(int64_t n, int64_t max_subjects, int64_t* out_ids);
 int swdrv_shuffle_replicas(int64_t M, int32_t shuffles);
 int swdrv_shuffle_permutation(int32_t L, uint32_t seed, int64_t id, int32_t replica, int32_t* out);
 
+/* Low-complexity masking of the subjects (an extension; DESIGN.md §16, include/cudasw4_amd_mask.h: the rule): what MMseqs2
+ * and DIAMOND do to their targets by default.  With masking on, every copy of subject chars that reaches a GPU — the resident
+ * or cached part once behind its upload, every streamed batch once behind each of its copies — is masked in place on the
+ * device before anything scans it; hit alignment, HSPs, PSSM building and the shuffled calibration see the same masked
+ * subjects (a masked column is an X op and code 20 in the counts), while the reference letters the driver reports stay raw.
+ * Call before the database is opened, like swdrv_set_shard: afterwards it fails.  window 4 .. 32; the entropies in bits,
+ * trigger_bits <= extend_bits; on = 0: off, and nothing is computed. */
+int swdrv_set_subject_masking(swdrv* d, int on, int32_t window, double trigger_bits, double extend_bits);
+/* The most recent complete pass over the DB, summed over the GPUs — the resident part's upload plus the streamed batches of
+ * the query collected last: positions covered by masked segments, subjects with a segment, true residues passed.  Zeros
+ * before any pass. */
+int swdrv_masking_counts(swdrv* d, uint64_t* positions, uint64_t* subjects, uint64_t* residues_seen);
+/* The rule alone (no GPU needed).  swdrv_mask_threshold: max(1, ceil(1024 W (log2 W - bits))).  swdrv_mask_subject: out[0 ..
+ * length) = the masked codes (out may be codes), returns the positions the segments cover, -1 for parameters out of range. */
+int32_t swdrv_mask_threshold(int32_t window, double bits);
+int64_t swdrv_mask_subject(const int8_t* codes, int32_t length, int32_t window, int32_t trigger_sum, int32_t extend_sum, int8_t* out);
+
 /* ---- input helpers (no GPU needed): what `align` does to its inputs before the scan ---- */
 
 /* ConvertAA_20 (convert.cuh:6-34): letters -> codes 0..20 */
