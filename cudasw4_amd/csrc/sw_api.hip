@@ -197,6 +197,8 @@ struct sw_ctx {
     int32_t stream_cols_max = 4096;       // most columns of a round of several slots
     int32_t stream_multi_cols_max = 1536; // ... of a multi-stripe query (its border arrays grow with the round)
     int32_t stream_multi_max_subject = -1;    // multi-stripe queries stream subjects up to this length (-1: 320 for fp16, 192 for int16)
+    int32_t chain = 3;                    // CUDASW4_AMD_CHAIN=1..8: batches a workgroup of the packed multi-stripe sw_scan_kernel claims at once and walks as one virtual subject per stripe (sw_dp_kernel.hpp: "Pair chains"; 1: one batch per claim).  3: the best of the sweep in profiles/pair_chain_results.md
+    bool chain_all = false;               // CUDASW4_AMD_CHAIN_ALL=1 (tests): every claim is a chain, also the last rounds of a launch and launches of few batches
     int32_t pipe_quorum = 0;              // (0: all tickets)
     int32_t pipe_slot = 0;                // sw_set_rows_pipeline_slot: VGPRs a stage occupies (128 / 168 / 256; 0: what it needs)
 };
@@ -320,6 +322,33 @@ size_t border_bytes_per_wg(int32_t lcap, int lanes) {
     // (16-lane groups: the border array and, behind it, the address stream of the packed sw_scan_kernel — 8 + 4 bytes per column)
     const size_t region = lanes == 16 ? swk::group_region_words<16>(lcap) : lanes == 8 ? swk::group_region_words<8>(lcap) : swk::group_region_words<64>(lcap);
     return (size_t)(swk::kThreads / lanes) * region * sizeof(uint32_t);
+}
+
+// Pair chains (sw_dp_kernel.hpp): the batches a claim of a launch takes.  Only the packed multi-stripe sw_scan_kernel on
+// 16-lane groups chains (plain ranges, one pair at a time: stream_slots == 1), and a launch of so few batches that none of
+// its claims would be a chain (the kernel's tail rule: more than chain * grid batches must remain) keeps today's scratch.
+// Measured at two points only (profiles/pair_chain_results.md): 5 batches per workgroup lose 0.6 % with chains of 3, 40 gain
+// 1.2 %; the threshold lies where the expected gain (1.3 % of the chained rounds) is about three times the loss seen at 5.
+constexpr int kChainMinRounds = 16;
+// Not measured: a chained border saves about 10 steps of a pair's walk (under 1 % from 1024 columns on), and the scratch
+// grows with the chain's columns.
+constexpr int32_t kChainMaxSubject = 1024;
+int chain_wanted(const sw_ctx* ctx, int kind, int lanes, bool multi, int stream_slots, int64_t nbatches, int32_t max_subject_len) {
+    if (!kind_packed(kind) || lanes != 16 || !multi || stream_slots != 1) return 1;
+    if (ctx->chain <= 1 || max_subject_len > kChainMaxSubject) return 1;
+    // ... and so does a launch of at most kChainMinRounds batches per workgroup: chained workgroups leave the lock-step of
+    // equal batches, which costs the end of a launch a fraction of a batch's walk, more than 1.3 % of a few rounds bring
+    // (125 000 subjects of 512 residues, 5 rounds: -0.6 % with chains of 3; profiles/pair_chain_results.md)
+    if (!ctx->chain_all && nbatches <= (int64_t)std::max(ctx->chain, kChainMinRounds) * max_grid(ctx)) return 1;
+    return std::min<int>(ctx->chain, swk::kChainMax);
+}
+// the border capacity of a chain's virtual subject, and a workgroup's scratch with it: the regions and the per-pair maxima
+int32_t chain_capacity(int32_t max_len, int chain, int lanes) {
+    return border_capacity((int32_t)std::min<int64_t>(swk::chain_columns(max_len, chain), SW_MAX_SUBJECT_LEN), lanes);
+}
+size_t chain_bytes_per_wg(int32_t max_len, int chain, int lanes) {
+    if (chain <= 1) return border_bytes_per_wg(border_capacity(max_len, lanes), lanes);
+    return border_bytes_per_wg(chain_capacity(max_len, chain, lanes), lanes) + (size_t)(swk::kThreads / lanes) * swk::kChainMaxWords * sizeof(uint32_t);
 }
 
 // Debug check of the max_subject_len contract (include/cudasw4_amd.h): longest subject of the range / of the listed positions
@@ -547,7 +576,17 @@ int scan_common(sw_ctx* ctx, int kind, int lanes, const int8_t* chars, const uin
             p.stream_cols = cols;
             p.lcap = border_capacity(std::max(max_subject_len, cols), lanes);
         }
-        const size_t per_wg = border_bytes_per_wg(p.lcap, lanes);
+        // pair chains: as many batches per claim as the caller's scratch holds for the whole grid (sw_scan_temp_bytes asks
+        // for the context's setting; a smaller scratch shortens the chains, down to one batch per claim)
+        int chain = (positions || count_ptr || list.claim || list.service_workgroups > 0) ? 1
+                        : chain_wanted(ctx, kind, lanes, multi, p.stream_slots, nbatches, max_subject_len);
+        while (chain > 1 && (size_t)grid * chain_bytes_per_wg(max_subject_len, chain, lanes) > temp_bytes) chain--;
+        if (chain > 1) {
+            p.chain = chain;
+            p.chain_all = ctx->chain_all ? 1 : 0;
+            p.lcap = chain_capacity(max_subject_len, chain, lanes);
+        }
+        const size_t per_wg = chain > 1 ? chain_bytes_per_wg(max_subject_len, chain, lanes) : border_bytes_per_wg(p.lcap, lanes);
         if (!temp || temp_bytes < per_wg) return fail(SW_ERR_TEMP, "temp buffer too small for a multi-stripe query");
         grid = (int)std::min<size_t>((size_t)grid, temp_bytes / per_wg);
         p.scratch = static_cast<uint32_t*>(temp);
@@ -738,6 +777,8 @@ int sw_ctx_create(int device, sw_ctx** out) {
     if (const char* e = getenv("CUDASW4_AMD_PIPE_TEST_DROP_STAGE")) ctx->pipe_drop_stage = atoi(e);
     if (const char* e = getenv("CUDASW4_AMD_PIPE_CPL")) ctx->pipe_cpl = atoi(e);
     if (const char* e = getenv("CUDASW4_AMD_STREAM")) ctx->stream_slots = std::max(0, std::min(swk::kStreamMaxSlots, atoi(e)));
+    if (const char* e = getenv("CUDASW4_AMD_CHAIN")) ctx->chain = std::max(1, std::min(swk::kChainMax, atoi(e)));
+    if (const char* e = getenv("CUDASW4_AMD_CHAIN_ALL")) ctx->chain_all = e[0] == '1';
     hipError_t e = hipMalloc(&ctx->d_matrix, 26 * swk::kLetters);
     if (e == hipSuccess) e = hipMalloc(&ctx->d_zeros, 256 + 64);  // + the word of the CUDASW4_AMD_CHECK_BOUNDS check (word 64) and the two of sw_streams_run_concurrently (72, 73)
     if (e == hipSuccess) e = hipMalloc(&ctx->d_work, 2 * kWorkSlots * sizeof(uint32_t));
@@ -1339,6 +1380,9 @@ static size_t scan_temp_bytes_of(sw_ctx* ctx, int kind, int part_id, int32_t n, 
     // default and almost every caller use; a scratch sized for fewer columns only makes the rounds shorter)
     const StreamPlan sp = stream_plan(ctx, kind, lanes, 1, pl, max_subject_len);
     const int32_t cols = sp.slots > 1 ? std::max(max_subject_len, sp.cols) : max_subject_len;
+    // pair chains (plain ranges only: part_id >= 0): regions for the chain's virtual subject, and the per-pair maxima
+    const int chain = part_id < 0 ? 1 : chain_wanted(ctx, kind, lanes, true, sp.slots, nbatches, max_subject_len);
+    if (chain > 1) return (size_t)grid * chain_bytes_per_wg(max_subject_len, chain, lanes);
     return (size_t)grid * border_bytes_per_wg(border_capacity(cols, lanes), lanes);
 }
 

@@ -443,6 +443,12 @@ struct ScanParams {
     // a*u in the kind's packed encoding (Arith::zero_at), u <= K + P; the kernel reads its window with scalar loads
     int32_t uniform_frame;
     int32_t flag_period;       // the column frame's period K (offs_possible): the uniform frame flags at least what it would
+    // Pair chains (packed multi-stripe sw_scan_kernel on 16-lane groups): a workgroup claims up to `chain` batches at once and
+    // its groups walk their pairs of those batches back to back, as one virtual subject per stripe (sw_scan_kernel: "Pair
+    // chains"; <= 1: one batch per claim); lcap and the scratch are sized for the chain (chain_region_words).  chain_all:
+    // every claim takes `chain` batches (tests) — otherwise only while more than chain * grid batches remain
+    int32_t chain;
+    int32_t chain_all;
     u32 levels[kLevelWords];
 };
 
@@ -894,6 +900,17 @@ constexpr int stream_region_words(int lcap) { return LANES == 16 ? Border<LANES>
 template <int LANES>
 constexpr int group_region_words(int lcap) { return border_region_words<LANES>(lcap) + stream_region_words<LANES>(lcap); }
 
+// Pair chains (sw_scan_kernel).  A chain of c pairs is one virtual subject: every pair but the last takes its longest
+// subject's columns rounded up to whole quads — at least kChainMinCols, so that the four reset quads of one border lie
+// before the first of the next — and four separator columns.  The border array and the address stream hold the virtual
+// subject (lcap = border capacity of chain_columns); behind the regions of all groups of the grid lie the per-pair maxima:
+// kChainMaxWords words per group, word 16 * k + lane = the running maximum (true scores) of pair k's cells in that lane.
+constexpr int kChainMax = 8;
+constexpr int kChainMinCols = 12;
+constexpr int kChainMaxWords = (kChainMax - 1) * kGroup;
+constexpr int chain_pair_columns(int lmax) { return ((lmax + 3) & ~3) < kChainMinCols ? kChainMinCols : ((lmax + 3) & ~3); }
+constexpr int64_t chain_columns(int max_len, int c) { return (int64_t)(c - 1) * (chain_pair_columns(max_len) + 4) + max_len; }
+
 // Start handshake (ScanParams::start_signal): this workgroup holds its registers and LDS now — whoever the caller ordered
 // behind the signal cannot take them
 __device__ __forceinline__ void announce_start(const ScanParams& p) {
@@ -949,8 +966,10 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
     static_assert(!A::kPacked || OFFS, "packed kinds run the column-offset recurrence only (sw_launch.hpp: launch_scan_ro)");
     constexpr bool kUni = A::kPacked;   // the packed kinds' frame (below)
     constexpr bool kAddr = A::kPacked && MULTI && LANES == 16;   // LDS addresses from the pair's address stream (stream_region_words)
+    constexpr bool kChain = kAddr;      // pair chains (below): the launches of these kernels are plain ranges (launch_scan_ro)
     constexpr int P = OFFS ? frame_classes(A::kPacked, R, LANES, MULTI, kUni) : 1;  // row classes of the column-offset frame
     __shared__ __attribute__((aligned(16))) unsigned char lds[16 + G::kTileBytes];
+    __shared__ int chainEnd[kChain ? (kThreads / 64) * kChainMax : 1];   // per wave: the virtual column behind pair k's last quad
     __shared__ __attribute__((aligned(16))) unsigned char rings[MULTI ? BD::ring_bytes(kGroups) : 16];
 
     const int tid = threadIdx.x;
@@ -971,6 +990,13 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
     constexpr int kSubjPerBatch = kGroups * A::kSubjects;
     const int nbatches = (n + kSubjPerBatch - 1) / kSubjPerBatch;
     if (!service && (int)blockIdx.x >= nbatches) return;  // workgroup-uniform (device-side count of the re-score path)
+    // Pair chains: claim c < nchain takes the batches kC * c .. kC * c + kC - 1 (the last one what is left of them), every
+    // later claim one batch — one atomic per claim either way.  Unless chain_all lifts the rule, a claim is a chain only
+    // while more than kC * gridDim.x batches remain: the last rounds of a launch hand out single batches as before, so the
+    // workgroups still finish within one pair's walk of each other
+    const int kC = kChain ? min(max(p.chain, 1), kChainMax) : 1;
+    const int nchain = (!kChain || kC == 1) ? 0 : p.chain_all ? (nbatches + kC - 1) / kC : max(0, (nbatches - kC * (int)gridDim.x + kC - 1) / kC);
+    const int nclaims = kChain ? nchain + max(0, nbatches - nchain * kC) : nbatches;
 
     if constexpr (!MULTI) {
         load_tile<G::kTileBytes>(lds, p.profile);
@@ -1048,55 +1074,82 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
                 }
                 avail = min(avail, n);
             }
-            if (b == nbatches && p.dry_signal) __hip_atomic_store(p.dry_signal, p.dry_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (b == nclaims && p.dry_signal) __hip_atomic_store(p.dry_signal, p.dry_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             next_batch = b;
             batch_avail = avail;
         }
         __syncthreads();
         const int b = next_batch;
-        if (b >= nbatches) break;
+        if (b >= nclaims) break;
         const int navail = batch_avail;
-        const int batch = service ? b : nbatches - 1 - b;  // DB is length-sorted ascending: longest first; a service walks its list as it grows
-        const int i0 = batch * kSubjPerBatch + group * A::kSubjects;
-        const int i1 = i0 + 1;
-        bool valid0 = i0 < navail;
-        bool valid1 = A::kPacked && (i1 < navail);
-        int pos0 = 0, pos1 = 0, len0 = 0, len1 = 0;
-        const int8_t* s0 = p.chars;
-        const int8_t* s1 = p.chars;
-        if (p.claim) {  // (32-bit kinds only: one subject per group; read by the group's lane 0, broadcast below)
-            int v = -1;
-            if (valid0 && lane == 0) v = claim_entry(i0);
-            if constexpr (LANES == 64) v = __builtin_amdgcn_readfirstlane(v);
-            else v = __shfl(v, (tid & 63) & ~(LANES - 1));
-            valid0 = v >= 0;
-            pos0 = valid0 ? v : 0;
-            if (valid0) {
-                len0 = p.lengths[pos0];
-                s0 = p.chars + (p.offsets[pos0] - p.offsets[0]);
-            }
-            valid1 = false;
-        } else {
-            if (valid0) {
-                pos0 = p.positions ? p.positions[i0] : p.first_pos + i0;
-                len0 = p.lengths[pos0];
-                s0 = p.chars + (p.offsets[pos0] - p.offsets[0]);
-            }
-            if (valid1) {
-                pos1 = p.positions ? p.positions[i1] : p.first_pos + i1;
-                len1 = p.lengths[pos1];
-                s1 = p.chars + (p.offsets[pos1] - p.offsets[0]);
-            }
+        // the claim's batches in hand-out order: hb .. hb + cnt - 1 (kChain: a chain of cnt pairs per group; else the one batch)
+        int hb = b, cnt = 1;
+        if constexpr (kChain) {
+            if (b < nchain) { hb = kC * b; cnt = min(kC, nbatches - hb); }
+            else hb = nchain * kC + (b - nchain);
+            hb = __builtin_amdgcn_readfirstlane(hb);
+            cnt = __builtin_amdgcn_readfirstlane(cnt);
         }
-        int lmax = len0 > len1 ? len0 : len1;
-        if constexpr (LANES <= 16) {  // the 4 (8) groups of a wave run in lock-step
-            if constexpr (LANES <= 4) lmax = max(lmax, __shfl_xor(lmax, 4));
-            if constexpr (LANES <= 8) lmax = max(lmax, __shfl_xor(lmax, 8));
-            lmax = max(lmax, __shfl_xor(lmax, 16));
-            lmax = max(lmax, __shfl_xor(lmax, 32));
-        }
+        // a group's pair of subjects of one batch; lmax: the longest subject of the wave's groups (they run in lock-step)
+        struct Pair {
+            bool valid0 = false, valid1 = false;
+            int pos0 = 0, pos1 = 0, len0 = 0, len1 = 0, lmax = 0;
+            const int8_t* s0 = nullptr;
+            const int8_t* s1 = nullptr;
+        };
+        auto load_pair = [&](int hbk) -> Pair {
+            Pair r;
+            const int batch = service ? hbk : nbatches - 1 - hbk;  // DB is length-sorted ascending: longest first; a service walks its list as it grows
+            const int i0 = batch * kSubjPerBatch + group * A::kSubjects;
+            const int i1 = i0 + 1;
+            r.valid0 = i0 < navail;
+            r.valid1 = A::kPacked && (i1 < navail);
+            r.s0 = p.chars;
+            r.s1 = p.chars;
+            if (p.claim) {  // (32-bit kinds only: one subject per group; read by the group's lane 0, broadcast below)
+                int v = -1;
+                if (r.valid0 && lane == 0) v = claim_entry(i0);
+                if constexpr (LANES == 64) v = __builtin_amdgcn_readfirstlane(v);
+                else v = __shfl(v, (tid & 63) & ~(LANES - 1));
+                r.valid0 = v >= 0;
+                r.pos0 = r.valid0 ? v : 0;
+                if (r.valid0) {
+                    r.len0 = p.lengths[r.pos0];
+                    r.s0 = p.chars + (p.offsets[r.pos0] - p.offsets[0]);
+                }
+                r.valid1 = false;
+            } else {
+                if (r.valid0) {
+                    r.pos0 = p.positions ? p.positions[i0] : p.first_pos + i0;
+                    r.len0 = p.lengths[r.pos0];
+                    r.s0 = p.chars + (p.offsets[r.pos0] - p.offsets[0]);
+                }
+                if (r.valid1) {
+                    r.pos1 = p.positions ? p.positions[i1] : p.first_pos + i1;
+                    r.len1 = p.lengths[r.pos1];
+                    r.s1 = p.chars + (p.offsets[r.pos1] - p.offsets[0]);
+                }
+            }
+            int lmax = r.len0 > r.len1 ? r.len0 : r.len1;
+            if constexpr (LANES <= 16) {  // the 4 (8) groups of a wave run in lock-step
+                if constexpr (LANES <= 4) lmax = max(lmax, __shfl_xor(lmax, 4));
+                if constexpr (LANES <= 8) lmax = max(lmax, __shfl_xor(lmax, 8));
+                lmax = max(lmax, __shfl_xor(lmax, 16));
+                lmax = max(lmax, __shfl_xor(lmax, 32));
+            }
+            r.lmax = lmax;
+            return r;
+        };
+        // (kChain: the pairs are looked up where they are needed — when the stream is written and when the scores are — so
+        // that nothing of them lives in registers across the stripes)
+        Pair pr;
+        if constexpr (!kChain) pr = load_pair(hb);
+        const bool valid0 = pr.valid0, valid1 = pr.valid1;
+        const int pos0 = pr.pos0, pos1 = pr.pos1, len0 = pr.len0, len1 = pr.len1;
+        const int8_t* const s0 = pr.s0;
+        const int8_t* const s1 = pr.s1;
         // the last lane finishes column lmax-1 at step lmax+LANES-2
-        int nquads = (lmax + LANES - 1 + 3) >> 2;
+        int nquads = (pr.lmax + LANES - 1 + 3) >> 2;
         // the border arrays hold lcap columns (sized from the caller's max_subject_len): never walk past them,
         // even if a caller under-reports the bound (scores of such subjects are then wrong, memory is not)
         if constexpr (MULTI) nquads = min(nquads, (p.lcap - 4) >> 2);
@@ -1116,17 +1169,33 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
             return w * (u32)G::kLetterUnits;
         };
         if constexpr (kAddr) {
-            // The pair's address stream (stream_region_words), once for all stripes: lane l writes the four words of columns
-            // 4c .. 4c + 3 for c = l, l + LANES, ... up to column 4 * nquads + LANES - 1, and the padding word of column
-            // l - LANES.  Each subject pads from its own end; a group without a subject B has len1 = 0.
+            // The address stream (stream_region_words), once for all stripes: lane l writes the four words of a pair's columns
+            // 4c .. 4c + 3 for c = l, l + LANES, ..., and the padding word of column l - LANES.  Each subject pads from its own
+            // end; a group without a subject B has len1 = 0.  A chain's pairs lie one behind the other, pair k from virtual
+            // column col0 on: its chain_pair_columns(lmax) columns and the separator quad (padding: behind both subjects'
+            // ends); the last pair as a single pair always was, up to column 4 * nquads + LANES - 1 of the virtual subject.
             u32* const sw = gBorder + border_region_words<LANES>(p.lcap) + LANES;   // the word of column 0
+            const int wcap = 4 * ((p.lcap - 4) >> 2) + LANES;                        // columns the region holds for the longest walk
             sw[lane - LANES] = (u32)(kPadLetter * G::kLetterUnits) * 0x01000100u;
-            for (int c = lane; c < nquads + LANES / 4; c += LANES) {
-                const u32 a = letters4(s0, len0pad, 4 * c), b = letters4(s1, len1pad, 4 * c);
+            auto put4 = [&](const Pair& q, int col0, int c) {
+                if (col0 + 4 * c + 4 > wcap) return;   // (a caller that under-reports the longest subject)
+                const u32 a = letters4(q.s0, (q.len0 + 3) & ~3, 4 * c), b = letters4(q.s1, (q.len1 + 3) & ~3, 4 * c);
                 // B's byte k -> bits 31:24, A's -> bits 15:8
-                *reinterpret_cast<uint4*>(sw + 4 * c) = make_uint4(__builtin_amdgcn_perm(b, a, 0x040c000cu), __builtin_amdgcn_perm(b, a, 0x050c010cu),
-                                                                   __builtin_amdgcn_perm(b, a, 0x060c020cu), __builtin_amdgcn_perm(b, a, 0x070c030cu));
+                *reinterpret_cast<uint4*>(sw + col0 + 4 * c) = make_uint4(__builtin_amdgcn_perm(b, a, 0x040c000cu), __builtin_amdgcn_perm(b, a, 0x050c010cu),
+                                                                          __builtin_amdgcn_perm(b, a, 0x060c020cu), __builtin_amdgcn_perm(b, a, 0x070c030cu));
+            };
+            int col0 = 0;
+            for (int k = 0; k + 1 < cnt; k++) {
+                const Pair q = load_pair(hb + k);
+                const int T = chain_pair_columns(__builtin_amdgcn_readfirstlane(q.lmax));
+                for (int c = lane; c < T / 4 + 1; c += LANES) put4(q, col0, c);
+                if ((tid & 63) == 0) chainEnd[(tid >> 6) * kChainMax + k] = col0 + T;
+                col0 += T + 4;
             }
+            const Pair q = load_pair(hb + cnt - 1);
+            nquads = (col0 + __builtin_amdgcn_readfirstlane(q.lmax) + LANES - 1 + 3) >> 2;
+            nquads = __builtin_amdgcn_readfirstlane(min(nquads, (p.lcap - 4) >> 2));
+            for (int c = lane; c < nquads - col0 / 4 + LANES / 4; c += LANES) put4(q, col0, c);
             // the group's own lanes read it, from the first stripe's acquire fence on (the border arrays travel the same way)
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         }
@@ -1160,8 +1229,10 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
                 // two steps back, one level below zw[lastClass] (fp16: may be -a; int16: >= 1024 - a)
                 st.upH_prev = A::gap(zw[(R - 1) % P], p.gex); st.Hlast = zw[(R - 1) % P]; st.Fout = zw[0];
                 // accumulator d holds the cells of frame zw[d + 1] (step q, class c: d = q + c); true score -> that frame
+                // (a chain starts with its first pair: maxv is its last pair's)
+                const u32 seed = (kChain && cnt > 1) ? 0u : maxv;
 #pragma unroll
-                for (int d = 0; d < P + 3; d++) st.maxv[d] = A::add(maxv, zw[d + 1]);
+                for (int d = 0; d < P + 3; d++) st.maxv[d] = A::add(seed, zw[d + 1]);
             } else {
                 // zero levels of the column before the lane's first one, per class (zc[k] = zbefore + a*k)
                 u32 zc[P + 5];
@@ -1339,8 +1410,68 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
                 }
                 if constexpr (kUni) load_levels(q + 1);
             };
+            // Pair chains: the hand-over from pair k to pair k + 1 of the virtual subject.  Pair k ends at virtual column E
+            // (chainEnd), four separator columns of the padding letter follow, pair k + 1 starts at column E + 4: lane l works on
+            // its last column of pair k at step E - 1 + l and on its first of pair k + 1 at step E + 4 + l, so the lanes 4j ..
+            // 4j + 3 are between the two at the top of quad E / 4 + j + 1 — where reset_lanes(k, j) turns them into the lanes
+            // of a fresh subject, under one exec mask and outside the four-step body:
+            //   * their maxima window becomes true scores (as at a stripe's end), which join the pair's running maximum of
+            //     the stripes above in the scratch (kChainMaxWords), and is seeded again at the levels of the quad to come;
+            //   * H, E, upH_prev, Hlast and Fout become what the stripe prologue sets: the state before this step of a lane
+            //     that has seen padding only.
+            // Everything else runs on across the border: the uniform frame and its lowering, the address stream, the border
+            // rings and blocks (positions of the virtual subject).  What a lane computes on separator columns before its reset
+            // continues pair k behind its end, like the padding behind a single pair (it raises no maximum); behind the reset
+            // it keeps the fresh state.  Lane 4j takes the row above from lane 4j - 1, which is one column ahead in pair k + 1
+            // already; lane 0 takes it from the stripe above, whose last lane went through the same virtual columns; only the
+            // diagonal of the first column (upH_prev) comes from the reset.  A lane that still is in pair k reads a reset
+            // neighbour's zero levels: nothing that could raise a maximum either.
+            auto reset_lanes = [&](int k, int j) {
+                if constexpr (kChain) {
+                    int t = tid;
+                    asm volatile("" : "+v"(t));   // (addresses rebuilt here, as in block_end)
+                    const int ln = t & (LANES - 1), grp = t / LANES;
+                    if ((ln >> 2) == j) {
+                        u32 m = A::true_of(st.maxv[0], zw[1]);
+#pragma unroll
+                        for (int d = 1; d < P + 3; d++) m = A::true_max(m, A::true_of(st.maxv[d], zw[d + 1]));
+                        u32* const pm = p.scratch + (size_t)gridDim.x * kGroups * (size_t)group_region_words<LANES>(p.lcap) +
+                                        ((size_t)blockIdx.x * kGroups + grp) * kChainMaxWords + kGroup * k + ln;
+                        if (!first) m = A::true_max(m, *pm);
+                        *pm = m;
+#pragma unroll
+                        for (int d = 0; d < P + 3; d++) st.maxv[d] = zw[d + 1];
+#pragma unroll
+                        for (int r = 0; r < R; r++) { st.H[r] = zw[r % P]; st.E[r] = zw[r % P + 1]; }
+                        st.upH_prev = A::gap(zw[(R - 1) % P], p.gex); st.Hlast = zw[(R - 1) % P]; st.Fout = zw[0];
+                    }
+                }
+            };
             if constexpr (!MULTI) {
                 for (int q = 0; q < nquads; q++) quad(q);
+            } else if constexpr (kChain) {
+                // block by block as below; the quad loop stops where lanes are handed over (wave-uniform scalars)
+                constexpr int kNever = 0x7fffffff;
+                const int* const ends = chainEnd + (tid >> 6) * kChainMax;
+                int rk = 0, rj = 0;
+                int nextReset = cnt > 1 ? __builtin_amdgcn_readfirstlane((ends[0] >> 2) + 1) : kNever;
+                for (int q0 = 0; q0 < nquads; q0 += BD::kQuadsPerBlock) {
+                    const int qend = min(nquads, q0 + BD::kQuadsPerBlock);
+                    int q = q0;
+                    for (;;) {
+                        const int seg = min(qend, nextReset);
+                        for (; q < seg; q++) quad(q);
+                        if (q >= qend) break;
+                        reset_lanes(rk, rj);   // q == nextReset: before quad q
+                        nextReset++;
+                        if (++rj == 4) {
+                            rj = 0;
+                            rk++;
+                            nextReset = rk + 1 < cnt ? __builtin_amdgcn_readfirstlane((ends[rk] >> 2) + 1) : kNever;
+                        }
+                    }
+                    if (qend == q0 + BD::kQuadsPerBlock) block_end(q0 / BD::kQuadsPerBlock);
+                }
             } else {
                 // multi-stripe: block by block (Border<LANES>: kQuadsPerBlock quads, then the block transfer)
                 for (int q0 = 0; q0 < nquads; q0 += BD::kQuadsPerBlock) {
@@ -1367,9 +1498,14 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
             }
             if constexpr (kUni) {
                 // accumulator d and zero level zw[d + 1] (the window of quad nquads) are in the same frame -> true scores
+                // (a chain's window was seeded without the stripes above at its last border)
+                const u32 above = maxv;
                 maxv = A::true_of(st.maxv[0], zw[1]);
 #pragma unroll
                 for (int d = 1; d < P + 3; d++) maxv = A::true_max(maxv, A::true_of(st.maxv[d], zw[d + 1]));
+                if constexpr (kChain) {
+                    if (cnt > 1) maxv = A::true_max(maxv, above);
+                }
             } else if constexpr (OFFS) {
                 if constexpr (A::kWindow) {
                     // accumulator d and zero level d are in the same frame -> true scores
@@ -1389,57 +1525,80 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
             if constexpr (MULTI) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         }
 
-        int sc0, sc1, guard = 0;
-        if constexpr (OFFS) {
-            // group maximum of true scores
-            if constexpr (LANES == 8) {
-                maxv = half_row_max(maxv, [](u32 a, u32 b) { return A::true_max(a, b); });
-            } else if constexpr (LANES == 4) {
-                maxv = quad_max(maxv, [](u32 a, u32 b) { return A::true_max(a, b); });
+        // a pair's scores from the lanes' maxima (true scores): nq the quads of its walk, col0 its first column in the walk
+        // (a chain's virtual subject; else 0)
+        auto finish = [&](bool valid0, bool valid1, int pos0, int pos1, u32 maxv, int nq, int col0) {
+            int sc0, sc1, guard = 0;
+            if constexpr (OFFS) {
+                // group maximum of true scores
+                if constexpr (LANES == 8) {
+                    maxv = half_row_max(maxv, [](u32 a, u32 b) { return A::true_max(a, b); });
+                } else if constexpr (LANES == 4) {
+                    maxv = quad_max(maxv, [](u32 a, u32 b) { return A::true_max(a, b); });
+                } else {
+                    maxv = row_max_true<KIND>(maxv);
+                }
+                if constexpr (LANES == 64) {
+                    maxv = A::true_max(maxv, (u32)__shfl_xor((int)maxv, 16));
+                    maxv = A::true_max(maxv, (u32)__shfl_xor((int)maxv, 32));
+                }
+                sc0 = A::true_lo(maxv);
+                sc1 = A::true_hi(maxv);
+                // no value of the alignment exceeded score + its cell's zero level: inside the exact range below the limit.  Column
+                // frame: a * (columns + 2 LANES + ...); uniform frame: a * (t_g + P + ...), t_g < 4 nquads + LANES (nstripes - 1) or K
+                if constexpr (kUni) {
+                    // (and never less than the column frame would: the same subjects are flagged and re-scored wherever that
+                    // bound is the larger one — in practice everywhere but short subjects of queries of many stripes)
+                    const int tgmax = 4 * nq + col0 + LANES * (p.nstripes - 1);
+                    constexpr int kColP = frame_classes(true, R, LANES, MULTI);
+                    guard = max(p.gex_mag * ((tgmax > 4 * rq ? 4 * rq : tgmax) + P + 8),
+                                p.gex_mag * (min(4 * nq, p.flag_period) + 2 * LANES + 4 + kColP));
+                } else {
+                    guard = p.gex_mag * (4 * nq + 2 * LANES + 4 + P);
+                }
             } else {
-                maxv = row_max_true<KIND>(maxv);
+                maxv = group_max<KIND, LANES>(maxv);
+                sc0 = A::score_lo(maxv);   // (32-bit kinds: one subject per group)
+                sc1 = 0;
             }
-            if constexpr (LANES == 64) {
-                maxv = A::true_max(maxv, (u32)__shfl_xor((int)maxv, 16));
-                maxv = A::true_max(maxv, (u32)__shfl_xor((int)maxv, 32));
+            if (lane == 0) {
+                if (valid0) {
+                    if (A::kPacked && p.ovf_check && sc0 >= A::kLimit - guard) {
+                        __hip_atomic_store(p.ovf_pos + atomicAdd(p.ovf_count, 1), pos0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    } else {
+                        p.scores[pos0] = (float)sc0;
+                        if (p.stat_count && sc0 >= p.stat_limit) atomicAdd(p.stat_count, 1);
+                    }
+                    p.ids[pos0] = (int32_t)(p.id_offset + pos0);
+                }
+                if (valid1) {
+                    if (p.ovf_check && sc1 >= A::kLimit - guard) {
+                        __hip_atomic_store(p.ovf_pos + atomicAdd(p.ovf_count, 1), pos1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    } else {
+                        p.scores[pos1] = (float)sc1;
+                    }
+                    p.ids[pos1] = (int32_t)(p.id_offset + pos1);
+                }
             }
-            sc0 = A::true_lo(maxv);
-            sc1 = A::true_hi(maxv);
-            // no value of the alignment exceeded score + its cell's zero level: inside the exact range below the limit.  Column
-            // frame: a * (columns + 2 LANES + ...); uniform frame: a * (t_g + P + ...), t_g < 4 nquads + LANES (nstripes - 1) or K
-            if constexpr (kUni) {
-                // (and never less than the column frame would: the same subjects are flagged and re-scored wherever that
-                // bound is the larger one — in practice everywhere but short subjects of queries of many stripes)
-                const int tgmax = 4 * nquads + LANES * (p.nstripes - 1);
-                constexpr int kColP = frame_classes(true, R, LANES, MULTI);
-                guard = max(p.gex_mag * ((tgmax > 4 * rq ? 4 * rq : tgmax) + P + 8),
-                            p.gex_mag * (min(4 * nquads, p.flag_period) + 2 * LANES + 4 + kColP));
-            } else {
-                guard = p.gex_mag * (4 * nquads + 2 * LANES + 4 + P);
+        };
+        if constexpr (kChain) {
+            int col0 = 0;
+            for (int k = 0; k < cnt; k++) {
+                const Pair q = load_pair(hb + k);
+                const int lm = __builtin_amdgcn_readfirstlane(q.lmax);
+                const bool lastPair = k + 1 == cnt;
+                int t = tid;
+                asm volatile("" : "+v"(t));
+                const u32* const pm = p.scratch + (size_t)gridDim.x * kGroups * (size_t)group_region_words<LANES>(p.lcap) +
+                                      ((size_t)blockIdx.x * kGroups + t / LANES) * kChainMaxWords + kGroup * k + (t & (LANES - 1));
+                u32 m = maxv;
+                if (!lastPair) m = *pm;
+                // (the early-flag bound of a pair from its own columns; the last pair's walk is what is left of the chain's)
+                finish(q.valid0, q.valid1, q.pos0, q.pos1, m, lastPair ? nquads - col0 / 4 : (lm + LANES - 1 + 3) >> 2, col0);
+                col0 += chain_pair_columns(lm) + 4;
             }
         } else {
-            maxv = group_max<KIND, LANES>(maxv);
-            sc0 = A::score_lo(maxv);   // (32-bit kinds: one subject per group)
-            sc1 = 0;
-        }
-        if (lane == 0) {
-            if (valid0) {
-                if (A::kPacked && p.ovf_check && sc0 >= A::kLimit - guard) {
-                    __hip_atomic_store(p.ovf_pos + atomicAdd(p.ovf_count, 1), pos0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                } else {
-                    p.scores[pos0] = (float)sc0;
-                    if (p.stat_count && sc0 >= p.stat_limit) atomicAdd(p.stat_count, 1);
-                }
-                p.ids[pos0] = (int32_t)(p.id_offset + pos0);
-            }
-            if (valid1) {
-                if (p.ovf_check && sc1 >= A::kLimit - guard) {
-                    __hip_atomic_store(p.ovf_pos + atomicAdd(p.ovf_count, 1), pos1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                } else {
-                    p.scores[pos1] = (float)sc1;
-                }
-                p.ids[pos1] = (int32_t)(p.id_offset + pos1);
-            }
+            finish(valid0, valid1, pos0, pos1, maxv, nquads, 0);
         }
     }
 }

@@ -93,7 +93,12 @@ int sw_set_query(sw_ctx* ctx, const int8_t* query_codes_host, int32_t qlen, void
  * for the CURRENT query (0 when the query fits one stripe).  sw_rescore_overflow: pass part_id = -1 and
  * n = max_count.  Replaces the reference's tempBytesPerBlockPerBuffer / tempBytesPerSubjectPerBuffer
  * sizing (cudasw4.cuh:1928-1938,2028-2033).  Launches that run concurrently on different streams need
- * separate temp buffers. */
+ * separate temp buffers.
+ * Large launches of the packed kinds with several stripes (more than 16 batches of 32 subjects per workgroup, subjects of
+ * up to 1024 residues) walk chains of CUDASW4_AMD_CHAIN (default 3) subject pairs back to back, and the scratch then holds a
+ * chain's columns: about 2.65 times the bytes of one pair per workgroup at the default.  A smaller temp buffer is no
+ * error as long as it holds one pair's scratch for one workgroup: the launch then runs shorter chains (down to one pair),
+ * and fewer workgroups, with the same results. */
 size_t sw_scan_temp_bytes(sw_ctx* ctx, int kind, int part_id, int32_t n, int32_t max_subject_len);
 
 /* One length partition of one batch: replaces call_NW_local_affine_{single,multi}_pass_*
@@ -112,7 +117,10 @@ size_t sw_scan_temp_bytes(sw_ctx* ctx, int kind, int part_id, int32_t n, int32_t
  *   max_subject_len upper bound of lengths[first_pos .. first_pos+n).  CONTRACT: it sizes the stripe-border scratch of
  *                   multi-stripe queries (sw_scan_temp_bytes) and the kernels never walk past that scratch, so an
  *                   under-reported bound is memory-safe but SILENTLY truncates longer subjects at the bound (their
- *                   scores are then those of the truncated subject).  Pass the true maximum (the reference passes the
+ *                   scores are then those of the truncated subject).  In a launch that walks chains of subject pairs
+ *                   (sw_scan_temp_bytes) the bound also places the pairs of a chain: under-reported, the scores of the
+ *                   OTHER subjects of a truncated subject's chain (up to CUDASW4_AMD_CHAIN x 32 neighbours in the range) are
+ *                   undefined too.  Pass the true maximum (the reference passes the
  *                   partition's boundary, cudasw4.cuh:1767-1912); over-reporting only costs scratch.
  *                   Debugging a binding: with CUDASW4_AMD_CHECK_BOUNDS=1 in the environment of sw_ctx_create every scan
  *                   and re-score first finds the longest subject of its range on the device (one small kernel and a
