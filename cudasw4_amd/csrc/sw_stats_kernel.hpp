@@ -5,7 +5,7 @@
 // 160 KiB).  A lane loads four subjects at a time (16 bytes of scores, 16 of lengths), adds them to the tile with integer
 // LDS atomics, and at the end the workgroup adds the non-zero words of its tile to the table in memory.
 //
-// The hazard is the one topk_hist_kernel (sw_api.hip) met: a DB is sorted by length and the scores of unrelated subjects
+// The hazard is the one topk_hist_kernel (sw_topk.hip) met: a DB is sorted by length and the scores of unrelated subjects
 // crowd into about 20 values, so the lanes of a wave hit a handful of LDS words, and 64 lanes adding to ONE word
 // serialise.  The remedy is the same: the lanes that share the first active lane's word add once, with their count.
 #pragma once

@@ -173,7 +173,7 @@ def test_topk_select_equals_sort_and_oracle(n, k, hi, monkeypatch):
     d_s = torch.from_numpy(scores_i.astype(np.float32)).cuda()
     d_i = torch.arange(1000, 1000 + n, dtype=torch.int32, device="cuda")  # ids need not equal positions
     got = {}
-    for path in ("sort", "select") + (("small",) if k <= 32 else ()):   # (round 6: two launches for k <= 32, sw_api.hip: topk_small_*)
+    for path in ("sort", "select") + (("small",) if k <= 32 else ()):   # (round 6: two launches for k <= 32, sw_topk.hip: topk_small_*)
         monkeypatch.setenv("CUDASW4_AMD_TOPK", path)
         tb = capi.topk_temp_bytes(n, k)
         temp = torch.empty(tb, dtype=torch.uint8, device="cuda")

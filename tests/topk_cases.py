@@ -1,6 +1,6 @@
 """Inputs and references for the top-K tests (tests/test_topk_cases_cpu.py, tests/test_gpu_topk.py).  numpy only: no GPU, no torch.
 
-sw_topk (cudasw4_amd/csrc/sw_api.hip, "top-K") returns the k best scores in descending order, equal scores in input
+sw_topk (cudasw4_amd/csrc/sw_topk.hip) returns the k best scores in descending order, equal scores in input
 (position) order, padded with (-1.0, -1) from index n on.  It has three implementations behind one entry point:
 
   small   k <= 32 and n > k: topk_small_partial_kernel (every workgroup walks chunks of 2 048 scores with its k best keys in
@@ -59,7 +59,7 @@ def k_for_position(scores_f32, p):
 
 
 def small_grid(n, num_cus):
-    """workgroups of topk_small_partial_kernel (sw_api.hip: small_grid)"""
+    """workgroups of topk_small_partial_kernel (sw_topk.hip: small_grid)"""
     nchunks = (n + CHUNK - 1) // CHUNK
     return max(1, min(nchunks, SMALL_MAX_GRID, max(1, num_cus) * 4))
 
