@@ -48,6 +48,9 @@ MAX_HSPS = 16
 SHUFFLE_EXPORTS = ["sw_shuffle_subjects"]
 # ... and include/cudasw4_amd_mask.h (low-complexity masking of the subjects on the device)
 MASK_EXPORTS = ["sw_mask_subjects", "sw_mask_subjects_phases"]
+# ... and include/cudasw4_amd_msa.h (the query-anchored MSA of a query's hits and its redundancy filter)
+MSA_EXPORTS = ["sw_msa_filter"]
+MSA_GAP, MSA_NONE, MSA_MAX_HITS = 21, 22, 1 << 15
 
 
 # sw_align_hits (include/cudasw4_amd.h): result records, statuses, flags, CIGAR op codes
@@ -408,6 +411,39 @@ def pssm_accumulate(ctx, query, qlen, n, chars, offsets, lengths, results, cigar
                             cigar or None, include or None, counts or None, weights or None, wcounts or None, used or None,
                             ctypes.cast(ev, ctypes.c_void_p) if ev is not None else None, stream or None)
     check(f(ctx.handle if ctx is not None else None, ctypes.byref(a)))
+
+
+class _MsaArgs(ctypes.Structure):
+    _fields_ = [("query", ctypes.c_void_p), ("qlen", ctypes.c_int32), ("n", ctypes.c_int32), ("chars", ctypes.c_void_p),
+                ("offsets", ctypes.c_void_p), ("lengths", ctypes.c_void_p), ("results", ctypes.c_void_p),
+                ("cigar", ctypes.c_void_p), ("include", ctypes.c_void_p), ("max_identity", ctypes.c_int32),
+                ("rows", ctypes.c_void_p), ("residues", ctypes.c_void_p), ("keep", ctypes.c_void_p), ("purged", ctypes.c_void_p),
+                ("pair_ident", ctypes.c_void_p), ("temp", ctypes.c_void_p), ("temp_bytes", ctypes.c_size_t),
+                ("temp_bytes_needed", ctypes.POINTER(ctypes.c_size_t)), ("phase_events", ctypes.c_void_p),
+                ("stream", ctypes.c_void_p)]
+
+
+def msa_filter(ctx, query, qlen, n, chars, offsets, lengths, results, cigar, include, max_identity, residues, keep, purged,
+               rows=0, pair_ident=0, temp=0, temp_bytes=0, stream=0, phase_events=None):
+    """sw_msa_filter (include/cudasw4_amd_msa.h): the rows of the query-anchored alignment of the n hits sw_align_hits /
+    sw_align_hits_pssm aligned (uint8, (n + 1) x qlen, the master last; optional), their residue counts (int32, n + 1), the
+    greedy redundancy filter at max_identity per cent (keep: uint8, n + 1; purged: int32, 1; 0 = no filter) and, for tests,
+    the pairwise identity counts (uint32, (n + 1) x (n + 1)).  Every buffer is a device pointer as an integer; query, include,
+    rows and pair_ident may be 0.  Asynchronous on `stream`.  phase_events: 4 hipEvent_t handles or None.
+    -> the temp bytes the call needs; with temp == 0 nothing is launched."""
+    if not hasattr(lib, "sw_msa_filter"):
+        raise SwError(-1, "this build of libcudasw4_amd.so has no sw_msa_filter")
+    f = lib.sw_msa_filter
+    if f.argtypes is None:   # bound on first use (CUDASW4_AMD_LIB may name an older build)
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(_MsaArgs)]
+    ev = (ctypes.c_void_p * 4)(*phase_events) if phase_events is not None else None
+    need = ctypes.c_size_t(0)
+    a = _MsaArgs(query or None, qlen, n, chars or None, offsets or None, lengths or None, results or None, cigar or None,
+                 include or None, max_identity, rows or None, residues or None, keep or None, purged or None, pair_ident or None,
+                 temp or None, temp_bytes, ctypes.pointer(need), ctypes.cast(ev, ctypes.c_void_p) if ev is not None else None,
+                 stream or None)
+    check(f(ctx.handle if ctx is not None else None, ctypes.byref(a)))
+    return int(need.value)
 
 
 def score_histogram(ctx, scores, lengths, n, hist, sumlen, skipped, stream=0):

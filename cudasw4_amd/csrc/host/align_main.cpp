@@ -18,9 +18,11 @@
 #include <string_view>
 #include <vector>
 
+#include "../../../include/cudasw4_amd_msa.h"
 #include "cli_options.hpp"
 #include "db_format.hpp"
 #include "hit_alignment.hpp"
+#include "hit_msa.hpp"
 #include "pssm_build.hpp"
 #include "pssm_query.hpp"
 #include "search_driver.hpp"
@@ -186,6 +188,56 @@ struct ShuffledStatistics {
 };
 ShuffledStatistics* shuffled = nullptr;   // (non-null under --statistics shuffled)
 
+// --outMsa: the query-anchored MSA of one query's reported results (hit_msa.hpp).  The aligner holds the
+// results' alignments of the query's last round on the device (already made for --alignments or by the last round's PSSM
+// build; made here otherwise); the filter runs there, the writer on the host.
+struct MsaOutput {
+    HitAligner* aligner = nullptr;
+    std::unique_ptr<HitMsa> msa;
+    // master: the query's letters (a PSSM query: the residue column of its file); pssm: what the results were scanned with
+    // (nullptr: the letters); alignments: nullptr when nothing has aligned the results yet
+    void write(const ProgramOptions& o, const SearchDriver& d, int64_t queryNum, std::string_view queryHeader, const std::string& master,
+               const int8_t* pssm, const ScanResult& r, const std::vector<HitAlignment>* alignments, const EvalueReport* ev) {
+        const int32_t qlen = int32_t(master.size());
+        std::vector<HitAlignment> own;
+        if (!alignments) {
+            own = pssm ? aligner->align(pssm, qlen, master.data(), r) : aligner->align(master.data(), qlen, r);
+            alignments = &own;
+        }
+        const size_t n = r.scores.size();
+        std::vector<uint8_t> shown(n, 1);   // (--maxEvalue: the results that are printed)
+        size_t reported = 0, noTrace = 0;
+        for (size_t i = 0; i < n; i++) {
+            shown[i] = !ev || ev->shows(ev->of(r, d, i));
+            reported += shown[i];
+            noTrace += shown[i] && (*alignments)[i].r.status == SW_ALIGN_NO_TRACE;
+        }
+        std::vector<uint8_t> keep(n, 0);
+        int32_t purged = 0;
+        if (n > 0) {
+            const MsaFilterResult f = msa->filter(master.data(), qlen, shown.data(), o.msaMaxIdentity, false);
+            keep.assign(f.keep.begin(), f.keep.begin() + long(n));
+            purged = f.purged;
+        }
+        std::vector<std::string> headers(n), letters(n);
+        for (size_t i = 0; i < n; i++)
+            if (keep[i]) {
+                headers[i] = std::string(d.getReferenceHeader(r.referenceIds[i]));
+                letters[i] = d.getReferenceSequence(r.referenceIds[i]);
+            }
+        MsaFormat format = MsaFormat::A3m;
+        parse_msa_format(o.msaFormat, format);
+        const std::string path = o.outMsa + "." + std::to_string(queryNum) + (format == MsaFormat::A3m ? ".a3m" : ".fasta");
+        std::string header(queryHeader);
+        if (!header.empty() && header[0] == '>') header.erase(0, 1);
+        const size_t written = write_msa(path, format, master, header, headers, letters, *alignments, keep.data());
+        if (o.verbose)
+            std::cout << "msa: " << written << " of " << reported << " results written, " << purged << " purged, " << noTrace
+                      << " without a trace\n";
+    }
+};
+MsaOutput* msaOut = nullptr;   // (non-null under --outMsa)
+
 // the fit of a scan made with the statistics on (--evalues / --maxEvalue / --inclusionEvalue): of the scan's own table, or
 // under --statistics shuffled the query's calibration with N from the scan's table
 SearchStats fitOf(const ScanResult& r) {
@@ -274,7 +326,8 @@ IterationResult runIterations(const ProgramOptions& o, SearchDriver& driver, Pss
         }
         out.built = builder.build(master.data(), qlen, scoring.empty() ? nullptr : scoring.data(), r.referenceIds.data(),
                                   r.scores.data(), r.scores.size(), o.inclusionScore, o.pseudocount, &info,
-                                  o.haveInclusionEvalue ? admitted.data() : nullptr, o.reportAlignments() ? o.maxHsps : 1, o.hspMinScore);
+                                  o.haveInclusionEvalue ? admitted.data() : nullptr, o.reportAlignments() ? o.maxHsps : 1, o.hspMinScore,
+                                  o.purgeIdentity);
         out.alignments = std::move(info.alignments);
         out.hsps = std::move(info.hsps);
         std::vector<int64_t> included;
@@ -286,7 +339,9 @@ IterationResult runIterations(const ProgramOptions& o, SearchDriver& driver, Pss
             std::cout << "Query " << queryNum << " round " << round << ": " << r.scores.size() << " results, " << info.used
                       << " in the PSSM, " << info.belowScore << (o.haveInclusionEvalue ? " above the inclusion E-value, " : " below the inclusion score, ")
                       << info.noTrace << " without a trace, "
-                      << info.copies << " copies of the query, lambda " << info.lambda
+                      << info.copies << " copies of the query"
+                      << (o.havePurgeIdentity ? ", " + std::to_string(info.purged) + " purged as redundant" : std::string())
+                      << ", lambda " << info.lambda
                       << (converged && round < o.iterations ? ", converged" : "") << "\n";
         if (round >= o.iterations || converged) break;
         previous = std::move(included);
@@ -342,7 +397,7 @@ void processQueryFile(const std::string& file, const ProgramOptions& o, SearchDr
         if (o.numTopOutputs > 0 || interactive) {
             std::vector<HitAlignment> alignments;
             HspLists lists;
-            if (aligner && iteration) {
+            if (iteration && (aligner || msaOut)) {
                 alignments = std::move(rounds.alignments);
                 lists = std::move(rounds.hsps);
             } else if (aligner && o.reportHsps()) lists = alignHsps(o, *aligner, q.sequence, nullptr, r, alignments);
@@ -360,6 +415,8 @@ void processQueryFile(const std::string& file, const ProgramOptions& o, SearchDr
             }
             out.flush();
             reportSignificant(o, r, driver, ev);
+            if (msaOut && !interactive)
+                msaOut->write(o, driver, q.num, q.header, q.sequence, nullptr, r, aligner || iteration ? &alignments : nullptr, ev);
         }
     };
     try {
@@ -400,7 +457,7 @@ void processPssmQuery(const PssmQuery& q, const ProgramOptions& o, SearchDriver&
     if (o.numTopOutputs > 0) {
         std::vector<HitAlignment> alignments;
         HspLists lists;
-        if (aligner && iteration) {
+        if (iteration && (aligner || msaOut)) {
             alignments = std::move(rounds.alignments);
             lists = std::move(rounds.hsps);
         } else if (aligner && o.reportHsps()) lists = alignHsps(o, *aligner, q.consensus, q.scores.data(), r, alignments);
@@ -417,6 +474,10 @@ void processPssmQuery(const PssmQuery& q, const ProgramOptions& o, SearchDriver&
         }
         out.flush();
         reportSignificant(o, r, driver, ev);
+        // (after the last round the results were scanned with the PSSM of the round before: the last build's alignments are
+        // against it; without rounds they are against the file's PSSM)
+        if (msaOut)
+            msaOut->write(o, driver, 0, q.name, q.consensus, q.scores.data(), r, aligner || iteration ? &alignments : nullptr, ev);
     }
     const BenchmarkStats total = driver.totalTimerStop();
     if (o.verbose) std::cout << "Total time: " << total.seconds << " s, " << total.gcups << " GCUPS\n";
@@ -467,6 +528,32 @@ int main(int argc, char** argv) {
         if (!(options.pseudocount > 0)) throw std::runtime_error("--pseudocount must be positive");
         if (options.buildsPssm() && options.interactive) throw std::runtime_error("--iterations / --outPssm cannot be combined with --interactive");
         if (options.buildsPssm() && options.numTopOutputs < 1) throw std::runtime_error("--iterations / --outPssm need --top of at least 1: the PSSM is built from the reported results");
+        {
+            auto percent = [](const std::string& text, const char* flag) {
+                size_t used = 0;
+                long v = 0;
+                try { v = std::stol(text, &used); } catch (...) { used = 0; }
+                if (text.empty() || used != text.size() || v < 1 || v > 100)
+                    throw std::runtime_error(std::string(flag) + " must be an integer in 1 .. 100, not '" + text + "'");
+                return int(v);
+            };
+            if ((options.haveMsaFormat || options.haveMsaMaxIdentity) && !options.haveOutMsa)
+                throw std::runtime_error("--msaFormat / --msaMaxIdentity need --outMsa PREFIX: they say how the multiple alignment is written");
+            if (options.haveOutMsa && options.outMsa.empty()) throw std::runtime_error("--outMsa needs a file prefix");
+            MsaFormat format;
+            if (!parse_msa_format(options.msaFormat, format))
+                throw std::runtime_error("--msaFormat must be a3m or fasta, not '" + options.msaFormat + "'");
+            if (options.haveMsaMaxIdentity) options.msaMaxIdentity = percent(options.msaMaxIdentityText, "--msaMaxIdentity");
+            if (options.havePurgeIdentity) options.purgeIdentity = percent(options.purgeIdentityText, "--purgeIdentity");
+            if (options.havePurgeIdentity && !options.buildsPssm())
+                throw std::runtime_error("--purgeIdentity needs --iterations above 1 or --outPssm: it says which results go into the PSSM");
+            if ((options.haveOutMsa || options.havePurgeIdentity) && options.interactive)
+                throw std::runtime_error("--outMsa / --msaFormat / --msaMaxIdentity / --purgeIdentity cannot be combined with --interactive");
+            if (options.haveOutMsa && options.numTopOutputs < 1)
+                throw std::runtime_error("--outMsa needs --top of at least 1: the alignment is made of the reported results");
+            if (options.haveOutMsa && options.numTopOutputs > SW_MSA_MAX_HITS)
+                throw std::runtime_error("--outMsa takes --top up to " + std::to_string(SW_MSA_MAX_HITS));
+        }
         if ((options.haveMaskWindow || options.haveMaskTrigger || options.haveMaskExtend) && !options.maskSubjects)
             throw std::runtime_error("--maskWindow / --maskTrigger / --maskExtend need --maskSubjects: they say how the subjects are masked");
         MaskParams maskParams;
@@ -539,10 +626,16 @@ int main(int argc, char** argv) {
             shuffled = &shuffledStorage;
         }
         std::unique_ptr<HitAligner> aligner;
-        if (options.reportAlignments() || options.buildsPssm()) aligner = std::make_unique<HitAligner>(driver);
+        if (options.reportAlignments() || options.buildsPssm() || options.writesMsa()) aligner = std::make_unique<HitAligner>(driver);
         std::unique_ptr<PssmBuilder> iteration;   // (non-null: every query goes through its rounds)
         if (options.buildsPssm()) iteration = std::make_unique<PssmBuilder>(driver, *aligner);
         HitAligner* const reporting = options.reportAlignments() ? aligner.get() : nullptr;   // (alignments are printed)
+        MsaOutput msaStorage;
+        if (options.writesMsa()) {
+            msaStorage.aligner = aligner.get();
+            msaStorage.msa = std::make_unique<HitMsa>(*aligner);
+            msaOut = &msaStorage;
+        }
 
         if (!options.interactive) {
             size_t nextPssm = 0;

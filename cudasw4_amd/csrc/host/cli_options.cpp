@@ -51,6 +51,10 @@ void printOptions(const ProgramOptions& o) {
     if (o.haveMaskTrigger) std::cout << "maskTrigger: " << o.maskTrigger << "\n";
     if (o.haveMaskExtend) std::cout << "maskExtend: " << o.maskExtend << "\n";
     if (!o.outPssm.empty()) std::cout << "outPssm: " << o.outPssm << "\n";
+    if (o.havePurgeIdentity) std::cout << "purgeIdentity: " << o.purgeIdentityText << "\n";
+    if (o.haveOutMsa) std::cout << "outMsa: " << o.outMsa << "\n";
+    if (o.haveMsaFormat) std::cout << "msaFormat: " << o.msaFormat << "\n";
+    if (o.haveMsaMaxIdentity) std::cout << "msaMaxIdentity: " << o.msaMaxIdentityText << "\n";
     std::cout << "blosum: " << substitution_matrix(o.matrix).name << "\n";
     std::cout << "singlePassType: " << to_string(o.kernels.singlePassType) << "\n";
     std::cout << "manyPassType_small: " << to_string(o.kernels.manyPassType_small) << "\n";
@@ -107,6 +111,10 @@ bool parseArgs(int argc, char** argv, ProgramOptions& o) {
         else if (arg == "--maskExtend") { o.maskExtend = value(i); o.haveMaskExtend = true; }
         else if (arg == "--pseudocount") o.pseudocount = std::atof(value(i).c_str());
         else if (arg == "--outPssm") o.outPssm = value(i);
+        else if (arg == "--purgeIdentity") { o.purgeIdentityText = value(i); o.havePurgeIdentity = true; }
+        else if (arg == "--outMsa") { o.outMsa = value(i); o.haveOutMsa = true; }
+        else if (arg == "--msaFormat") { o.msaFormat = value(i); o.haveMsaFormat = true; }
+        else if (arg == "--msaMaxIdentity") { o.msaMaxIdentityText = value(i); o.haveMsaMaxIdentity = true; }
         else if (arg == "--printLengthPartitions") o.printLengthPartitions = true;
         else if (arg == "--prefetchDBFile") o.prefetchDBFile = true;
         else if (arg == "--top") o.numTopOutputs = std::atoi(value(i).c_str());
@@ -179,7 +187,17 @@ void printHelp(char** argv) {
                  "        this option or --inclusionEvalue, not both.\n";
     std::cout << "      --inclusionEvalue X : Results with an E-value of at most X, under the statistics of the round's own scan, go into the PSSM.\n";
     std::cout << "      --pseudocount B : Weight of the substitution-matrix pseudo-frequencies, B > 0. Default val = " << d.pseudocount << "\n";
-    std::cout << "      --outPssm PREFIX : Write the PSSM built from the last round's results to PREFIX.<query number>.pssm (NCBI ASCII, as --pssm reads)\n\n";
+    std::cout << "      --outPssm PREFIX : Write the PSSM built from the last round's results to PREFIX.<query number>.pssm (NCBI ASCII, as --pssm reads)\n";
+    std::cout << "      --purgeIdentity P : Before the results are weighted, leave out every one that is at least P per cent identical, over its own\n"
+                 "        aligned residues, to the query or to a result that went in before it (P in 1 .. 100; PSI-BLAST purges at 94).\n"
+                 "        Needs --iterations above 1 or --outPssm. Default: nothing is purged, the weights alone handle redundancy\n\n";
+    std::cout << "   Multiple alignment\n";
+    std::cout << "      --outMsa PREFIX : Write the query-anchored multiple alignment of every query's reported results (of the last round, against\n"
+                 "        that round's scoring; first alignments only) to PREFIX.<query number>.a3m. Aligns the results itself without --alignments\n";
+    std::cout << "      --msaFormat a3m|fasta : a3m (default): insertions relative to the query in lower case. fasta: insertions left out, every\n"
+                 "        line as long as the query; the file is PREFIX.<query number>.fasta. Needs --outMsa\n";
+    std::cout << "      --msaMaxIdentity P : Write only results that are less than P per cent identical to the query and to every result written\n"
+                 "        before them (P in 1 .. 100, a greedy filter on the GPU). Needs --outMsa. Default: every aligned result is written\n\n";
     std::cout << "   Search statistics\n";
     std::cout << "      --evalues : Report a Z-score and an E-value with every result: the scores of the whole scan are regressed on the\n"
                  "        logarithm of the subject length (as FASTA / SSEARCH do), fitted per query on the GPU's score histogram. Two more TSV\n"

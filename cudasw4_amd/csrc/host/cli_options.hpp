@@ -72,6 +72,16 @@ struct ProgramOptions {
     bool maskSubjects = false;
     bool haveMaskWindow = false, haveMaskTrigger = false, haveMaskExtend = false;
     std::string maskWindow = "12", maskTrigger = "1.9", maskExtend = "2.2";
+    // The query-anchored MSA of a query's results (hit_msa.hpp; an extension): --outMsa PREFIX writes
+    // PREFIX.<query number>.a3m (--msaFormat fasta: .fasta) from the reported results of the query's last round; --msaMaxIdentity P
+    // leaves out results that are at least P per cent identical to the query or to a result written before them;
+    // --purgeIdentity P does the same to the results that go into a PSSM.  The values are kept as given and checked in main,
+    // before any device is opened (which fills the two numbers; 0: no filter).
+    std::string outMsa;
+    bool haveOutMsa = false, haveMsaFormat = false, haveMsaMaxIdentity = false, havePurgeIdentity = false;
+    std::string msaFormat = "a3m", msaMaxIdentityText, purgeIdentityText;
+    int msaMaxIdentity = 0, purgeIdentity = 0;
+    bool writesMsa() const { return haveOutMsa; }
     bool prefetchDBFile = false;
     int numTopOutputs = 10;
     int gop = -11;

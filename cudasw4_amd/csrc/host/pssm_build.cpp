@@ -119,11 +119,12 @@ void* PssmBuilder::grow(int slot, size_t bytes) {
 
 std::vector<int8_t> PssmBuilder::build(const char* master, int32_t qlen, const int8_t* pssm, const int64_t* ids,
                                        const int32_t* scores, size_t n, int32_t minScore, double pseudocount, PssmBuildInfo* info,
-                                       const uint8_t* admitted, int maxHsps, int hspMinScore) {
+                                       const uint8_t* admitted, int maxHsps, int hspMinScore, int purgeIdentity) {
     if (qlen < 1 || !master) throw std::runtime_error("PSSM build: empty master sequence");
     if (qlen > (1 << 20)) throw std::runtime_error("PSSM build: queries longer than 2^20 residues are not supported");
     if (n > 0 && (!ids || !scores)) throw std::runtime_error("PSSM build: null hit list");
     if (!(pseudocount > 0)) throw std::runtime_error("PSSM build: the pseudocount must be positive");
+    if (purgeIdentity < 0 || purgeIdentity > 100) throw std::runtime_error("PSSM build: the purge identity must lie in 0 .. 100");
     PssmBuildInfo local;
     PssmBuildInfo& I = info ? *info : local;
     I = PssmBuildInfo();
@@ -149,6 +150,17 @@ std::vector<int8_t> PssmBuilder::build(const char* master, int32_t qlen, const i
             I.included[h] = 1;
             expectUsed++;
         }
+    }
+    if (purgeIdentity > 0 && n > 0) {
+        // the redundancy filter on the hits that passed, with their include bytes: include[h] &= keep[h]
+        if (!msa_) msa_ = std::make_unique<HitMsa>(aligner_);
+        const MsaFilterResult f = msa_->filter(master, qlen, I.included.data(), purgeIdentity, false);
+        I.purged = f.purged;
+        for (size_t h = 0; h < n; h++)
+            if (I.included[h] && !f.keep[h]) {
+                I.included[h] = 0;
+                expectUsed--;
+            }
     }
     std::vector<int8_t> codes(static_cast<size_t>(qlen));
     for (int32_t i = 0; i < qlen; i++) codes[size_t(i)] = encode_residue(master[i]);
@@ -197,6 +209,36 @@ std::vector<int8_t> PssmBuilder::build(const char* master, int32_t qlen, const i
 }  // namespace swh
 
 #ifdef SWH_DRIVER_CAPI   // libcudasw4_host.so (with driver_capi.cpp); `align` links the functions above alone
+namespace {
+int build_pssm_capi(swdrv* d, const char* master_letters, int32_t qlen, const int8_t* pssm, const int64_t* ids, const int32_t* scores,
+                    int n, int32_t min_score, double pseudocount, int purge_identity, int8_t* pssm_out, swdrv_pssm_info* info_out,
+                    int32_t* purged_out) {
+    try {
+        if (!d || !d->driver) throw std::runtime_error("null driver");
+        if (n < 0 || !pssm_out) throw std::runtime_error("bad arguments");
+        swh::HitAligner aligner(*d->driver);
+        swh::PssmBuilder builder(*d->driver, aligner);
+        swh::PssmBuildInfo info;
+        const std::vector<int8_t> out = builder.build(master_letters, qlen, pssm, ids, scores, size_t(n), min_score, pseudocount, &info,
+                                                      nullptr, 1, 1, purge_identity);
+        std::copy(out.begin(), out.end(), pssm_out);
+        if (info_out) {
+            info_out->used = info.used;
+            info_out->below_score = info.belowScore;
+            info_out->no_trace = info.noTrace;
+            info_out->copies = info.copies;
+            info_out->lambda = info.lambda;
+            if (info_out->included) std::copy(info.included.begin(), info.included.end(), info_out->included);
+        }
+        if (purged_out) *purged_out = info.purged;
+        return 0;
+    } catch (const std::exception& e) {
+        swh::set_driver_error(e.what());
+        return -1;
+    }
+}
+}  // namespace
+
 extern "C" int swdrv_pssm_from_counts(int matrix, const int8_t* master_codes, int32_t qlen, const uint32_t* counts,
                                       const uint64_t* wcounts, double pseudocount, int8_t* pssm_out, double* raw_out,
                                       double* lambda_out) {
@@ -216,26 +258,13 @@ extern "C" int swdrv_pssm_from_counts(int matrix, const int8_t* master_codes, in
 extern "C" int swdrv_build_pssm(swdrv* d, const char* master_letters, int32_t qlen, const int8_t* pssm, const int64_t* ids,
                                 const int32_t* scores, int n, int32_t min_score, double pseudocount, int8_t* pssm_out,
                                 swdrv_pssm_info* info_out) {
-    try {
-        if (!d || !d->driver) throw std::runtime_error("null driver");
-        if (n < 0 || !pssm_out) throw std::runtime_error("bad arguments");
-        swh::HitAligner aligner(*d->driver);
-        swh::PssmBuilder builder(*d->driver, aligner);
-        swh::PssmBuildInfo info;
-        const std::vector<int8_t> out = builder.build(master_letters, qlen, pssm, ids, scores, size_t(n), min_score, pseudocount, &info);
-        std::copy(out.begin(), out.end(), pssm_out);
-        if (info_out) {
-            info_out->used = info.used;
-            info_out->below_score = info.belowScore;
-            info_out->no_trace = info.noTrace;
-            info_out->copies = info.copies;
-            info_out->lambda = info.lambda;
-            if (info_out->included) std::copy(info.included.begin(), info.included.end(), info_out->included);
-        }
-        return 0;
-    } catch (const std::exception& e) {
-        swh::set_driver_error(e.what());
-        return -1;
-    }
+    return build_pssm_capi(d, master_letters, qlen, pssm, ids, scores, n, min_score, pseudocount, 0, pssm_out, info_out, nullptr);
+}
+
+extern "C" int swdrv_build_pssm_purged(swdrv* d, const char* master_letters, int32_t qlen, const int8_t* pssm, const int64_t* ids,
+                                       const int32_t* scores, int n, int32_t min_score, double pseudocount, int purge_identity,
+                                       int8_t* pssm_out, swdrv_pssm_info* info_out, int32_t* purged_out) {
+    return build_pssm_capi(d, master_letters, qlen, pssm, ids, scores, n, min_score, pseudocount, purge_identity, pssm_out, info_out,
+                           purged_out);
 }
 #endif

@@ -4,9 +4,11 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <vector>
 
 #include "hit_alignment.hpp"
+#include "hit_msa.hpp"
 #include "search_driver.hpp"
 #include "sequence_codec.hpp"
 
@@ -30,6 +32,7 @@ struct PssmBuildInfo {
     int32_t belowScore = 0;   // left out: scan score below the inclusion score
     int32_t noTrace = 0;      // left out: SW_ALIGN_NO_TRACE
     int32_t copies = 0;       // left out: a copy of the master
+    int32_t purged = 0;       // left out: redundant to the master or to an earlier hit that went in (purgeIdentity > 0)
     double lambda = 0;
     std::vector<uint8_t> included;   // one byte per hit: 1 where it took part
     std::vector<HitAlignment> alignments;   // the hits as they were aligned for this step
@@ -51,14 +54,17 @@ public:
     // that takes the place of the score test (inclusion by E-value: 0 = left out, counted in belowScore).  -> qlen x 21 int8
     // maxHsps > 1: the hits are aligned with up to maxHsps alignments each, the further ones scoring at least hspMinScore
     // (info->hsps); the PSSM is built from the first alignments (HitAligner::resident()) and is the one of maxHsps == 1.
+    // purgeIdentity P in 1 .. 100 (0: none): the hits that pass the rules above go through the redundancy filter of
+    // sw_msa_filter (hit_msa.hpp), in rank order behind the master, and the purged ones are left out before the weighting.
     std::vector<int8_t> build(const char* master, int32_t qlen, const int8_t* pssm, const int64_t* ids, const int32_t* scores,
                               size_t n, int32_t minScore, double pseudocount, PssmBuildInfo* info, const uint8_t* admitted = nullptr,
-                              int maxHsps = 1, int hspMinScore = 1);
+                              int maxHsps = 1, int hspMinScore = 1, int purgeIdentity = 0);
 
 private:
     void* grow(int slot, size_t bytes);
     const SearchDriver& d_;
     HitAligner& aligner_;
+    std::unique_ptr<HitMsa> msa_;   // made by the first build with purgeIdentity > 0
     int device_ = -1;
     enum { kMaster, kInclude, kCounts, kWeights, kWcounts, kUsed, kBuffers };
     void* buf_[kBuffers] = {};

@@ -116,6 +116,7 @@ __device__ __forceinline__ void walk_hit(const BuildParams& p, const int32_t h, 
     }
 }
 
+#ifndef SWB_WALKER_ONLY   // (sw_msa_kernel.hpp takes the parameters, the participation rule and the walker, not the kernels)
 // blocks [0, n): the hits; the blocks behind them: kMasterSpan positions of the master row each
 __global__ __launch_bounds__(kLanes) void pssm_count_kernel(const BuildParams p) {
     const int lane = threadIdx.x;
@@ -170,5 +171,6 @@ __global__ __launch_bounds__(kLanes) void pssm_weight_kernel(const BuildParams p
         if (a >= 0 && a < kLetters) atomicAdd(p.wcounts + (size_t)i * kLetters + a, w);
     }
 }
+#endif   // SWB_WALKER_ONLY
 
 }  // namespace swb

@@ -25,6 +25,7 @@ EXPORTS = ["swdrv_last_error", "swdrv_create", "swdrv_destroy", "swdrv_open_db",
            "swdrv_tail_overlaps", "swdrv_prefers_two_in_flight", "swdrv_pipeline_launches", "swdrv_handshake_active", "swdrv_preferred_in_flight",
            "swdrv_latency_scans", "swdrv_plan_runs_mode", "swdrv_align_hits", "swdrv_scan_pssm", "swdrv_scan_submit_pssm",
            "swdrv_align_hits_pssm", "swdrv_align_hsps", "swdrv_align_hsps_pssm", "swdrv_pssm_from_counts", "swdrv_build_pssm", "swdrv_write_pssm_ascii",
+           "swdrv_build_pssm_purged", "swdrv_hit_msa", "swdrv_write_msa",
            "swdrv_set_statistics", "swdrv_last_statistics", "swdrv_stats_from_histogram", "swdrv_evalues", "swdrv_length_bin",
            "swdrv_set_ranking", "swdrv_last_ranking", "swdrv_zscore_for_evalue", "swdrv_rank_order",
            "swdrv_calibrate_shuffled", "swdrv_calibrate_shuffled_pssm", "swdrv_set_rank_fit", "swdrv_shuffle_sample",
@@ -204,6 +205,39 @@ def _build_fns():
                        ctypes.POINTER(_PssmInfo)]
         wr.argtypes = [ctypes.c_char_p, vp, ctypes.c_int32, ctypes.c_char_p]
     return fc, bp, wr
+
+
+def _msa_fns():
+    """swdrv_build_pssm_purged / swdrv_hit_msa / swdrv_write_msa, bound on first use (like swdrv_align_hits: not in every build
+    of this C ABI)"""
+    bp, hm, wr = lib.swdrv_build_pssm_purged, lib.swdrv_hit_msa, lib.swdrv_write_msa
+    if bp.argtypes is None:
+        vp, i, cp = ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p
+        bp.argtypes = [vp, cp, ctypes.c_int32, vp, vp, vp, i, ctypes.c_int32, ctypes.c_double, i, vp, ctypes.POINTER(_PssmInfo),
+                       ctypes.POINTER(ctypes.c_int32)]
+        hm.argtypes = [vp, cp, ctypes.c_int32, vp, vp, vp, i, i, cp, cp, i, vp, vp, ctypes.c_int64, vp, vp, vp,
+                       ctypes.POINTER(ctypes.c_int32)]
+        wr.argtypes = [cp, i, cp, cp, i, ctypes.POINTER(cp), ctypes.POINTER(cp), vp, vp, vp]
+    return bp, hm, wr
+
+
+MSA_FORMATS = {"a3m": 0, "fasta": 1}
+
+
+def write_msa(path, fmt, master_letters, query_header, headers, subject_letters, results, cigar, keep=None):
+    """swdrv_write_msa: the A3M (fmt 'a3m') or FASTA ('fasta') file `align --outMsa` writes, from alignments the caller has:
+    results (capi.align_result_dtype() records whose cigar_offset index the uint32 words `cigar`), the hits' headers and RAW
+    letters, keep (one byte per hit, None: every hit).  No GPU needed."""
+    from . import capi
+    n = len(headers)
+    res = np.ascontiguousarray(results, dtype=capi.align_result_dtype())
+    cig = np.ascontiguousarray(cigar, dtype=np.uint32)
+    k = np.ascontiguousarray(keep, dtype=np.uint8) if keep is not None else None
+    enc = lambda t: t if isinstance(t, bytes) else t.encode()
+    hs = (ctypes.c_char_p * max(n, 1))(*[enc(h) for h in headers])
+    ss = (ctypes.c_char_p * max(n, 1))(*[enc(x) for x in subject_letters])
+    _check(_msa_fns()[2](enc(path), MSA_FORMATS[fmt], enc(master_letters), enc(query_header), n, hs, ss, res.ctypes.data,
+                         cig.ctypes.data, k.ctypes.data if k is not None else None))
 
 
 STATS_OK, STATS_NO_FIT = 0, 1
@@ -907,22 +941,72 @@ class Driver:
         cigars = [capi.cigar_string(cigar[int(r["cigar_offset"]):int(r["cigar_offset"]) + int(r["cigar_len"])]) for r in res]
         return res, cigars
 
-    def build_pssm(self, query_letters, result, pssm=None, min_score=0, pseudocount=10.0, max_evalue=None):
+    def hit_msa(self, query_letters, result, max_identity=None, pssm=None, consensus=None, fmt="a3m", query_header="query"):
+        """The query-anchored multiple alignment of the hits of `result` (swdrv_hit_msa): the hits are aligned as
+        align_hits aligns them — with `pssm` given as align_hits_pssm does, `query_letters` (or `consensus`) being the master —
+        and the rows, residue counts and the greedy redundancy filter are computed on the GPU from what the aligner left there.
+        max_identity: None (no filter) or 1 .. 100.
+        -> dict: rows ((n + 1, qlen) uint8, row n the master; 0..19 residue, 20 other, 21 gap, 22 none), residues (n + 1),
+        keep (n + 1), purged, a3m (the text `align --outMsa` writes for the kept hits), results, cigars"""
+        import tempfile
+        from . import capi, pssm as _pssm
+        master = consensus if consensus is not None else query_letters
+        if isinstance(master, str):
+            master = master.encode()
+        qlen = len(master)
+        P = 0 if max_identity is None else int(max_identity)
+        if max_identity is not None and not 1 <= P <= 100:
+            raise ValueError("max_identity must lie in [1, 100]")
+        scored_with = None
+        if pssm is not None:
+            scored_with = _pssm.as_pssm(pssm)
+            if scored_with.shape[0] != qlen:
+                raise ValueError("the master has %d residues, the PSSM %d rows" % (qlen, scored_with.shape[0]))
+        ids = np.ascontiguousarray(result["ids"], dtype=np.int64)
+        scores = np.ascontiguousarray(result["scores"], dtype=np.int32)
+        n = len(ids)
+        res = np.zeros(max(n, 1), dtype=capi.align_result_dtype())
+        cap = sum(qlen + self.reference_length(int(i)) for i in ids)
+        cigar = np.zeros(max(cap, 1), dtype=np.uint32)
+        rows = np.zeros((n + 1, max(qlen, 1)), dtype=np.uint8)
+        residues = np.zeros(n + 1, dtype=np.int32)
+        keep = np.zeros(n + 1, dtype=np.uint8)
+        purged = ctypes.c_int32(0)
+        with tempfile.TemporaryDirectory() as tmp:
+            path = os.path.join(tmp, "hits." + fmt)
+            _check(_msa_fns()[1](self.handle, master, qlen, scored_with.ctypes.data if scored_with is not None else None,
+                                 ids.ctypes.data, scores.ctypes.data, n, P, query_header.encode(), path.encode(), MSA_FORMATS[fmt],
+                                 res.ctypes.data, cigar.ctypes.data, cap, rows.ctypes.data, residues.ctypes.data, keep.ctypes.data,
+                                 ctypes.byref(purged)))
+            with open(path) as f:
+                text = f.read()
+        res = res[:n]
+        cigars = [capi.cigar_string(cigar[int(r["cigar_offset"]):int(r["cigar_offset"]) + int(r["cigar_len"])]) for r in res]
+        return {"rows": rows, "residues": residues, "keep": keep, "purged": int(purged.value), "a3m": text, "results": res,
+                "cigars": cigars}
+
+    def build_pssm(self, query_letters, result, pssm=None, min_score=0, pseudocount=10.0, max_evalue=None, purge_identity=None):
         """One step of an iterated search (swdrv_build_pssm): the hits of `result` — a scan of `query_letters`, or with
         `pssm` given a scan_pssm of it, `query_letters` being the master sequence — aligned, filtered (score >= min_score,
         with a CIGAR, not a copy of the master), accumulated on the GPU and converted.
         max_evalue: in place of the min_score test a hit takes part when its E-value under the fit of `result`'s own scan is
         at most max_evalue (`result` must come from a scan with set_statistics(True); under NO_FIT no hit takes part); the
         other rules are unchanged, and info's below_score counts the hits the E-value left out.
+        purge_identity: None, or P in 1 .. 100 (swdrv_build_pssm_purged): the hits that pass those rules go through the greedy
+        redundancy filter of hit_msa in rank order, and those at least P per cent identical to the master or to an earlier
+        hit that went in are left out before the weighting; info["purged"] counts them.
         -> ((qlen, 21) int8 PSSM, info dict: used, below_score, no_trace, copies, lambda, included = ids that took part)"""
         from . import pssm as _pssm
+        if purge_identity is not None and not 1 <= int(purge_identity) <= 100:
+            raise ValueError("purge_identity must lie in [1, 100]")
         if max_evalue is not None:
             if "evalues" not in result:
                 raise ValueError("max_evalue needs a result with E-values: set_statistics(True) before the scan")
             ev = np.asarray(result["evalues"])
             keep = (ev >= 0) & (ev <= float(max_evalue))
             kept = {"ids": np.asarray(result["ids"])[keep], "scores": np.asarray(result["scores"])[keep]}
-            built, info = self.build_pssm(query_letters, kept, pssm=pssm, min_score=0, pseudocount=pseudocount)
+            built, info = self.build_pssm(query_letters, kept, pssm=pssm, min_score=0, pseudocount=pseudocount,
+                                          purge_identity=purge_identity)
             info["below_score"] += int(len(keep) - keep.sum())
             return built, info
         if isinstance(query_letters, str):
@@ -939,17 +1023,27 @@ class Driver:
         out = np.zeros((max(qlen, 1), 21), dtype=np.int8)
         flags = np.zeros(max(n, 1), dtype=np.uint8)
         info = _PssmInfo(included=flags.ctypes.data)
-        _check(_build_fns()[1](self.handle, query_letters, qlen, scored_with.ctypes.data if scored_with is not None else None,
-                               ids.ctypes.data, scores.ctypes.data, n, int(min_score), float(pseudocount), out.ctypes.data,
-                               ctypes.byref(info)))
-        return out[:qlen], {"used": info.used, "below_score": info.below_score, "no_trace": info.no_trace, "copies": info.copies,
-                            "lambda": info.lambda_, "included": [int(i) for i, f in zip(ids, flags[:n]) if f]}
+        purged = ctypes.c_int32(0)
+        if purge_identity is None:
+            _check(_build_fns()[1](self.handle, query_letters, qlen, scored_with.ctypes.data if scored_with is not None else None,
+                                   ids.ctypes.data, scores.ctypes.data, n, int(min_score), float(pseudocount), out.ctypes.data,
+                                   ctypes.byref(info)))
+        else:
+            _check(_msa_fns()[0](self.handle, query_letters, qlen, scored_with.ctypes.data if scored_with is not None else None,
+                                 ids.ctypes.data, scores.ctypes.data, n, int(min_score), float(pseudocount), int(purge_identity),
+                                 out.ctypes.data, ctypes.byref(info), ctypes.byref(purged)))
+        built = {"used": info.used, "below_score": info.below_score, "no_trace": info.no_trace, "copies": info.copies,
+                 "lambda": info.lambda_, "included": [int(i) for i, f in zip(ids, flags[:n]) if f]}
+        if purge_identity is not None:
+            built["purged"] = int(purged.value)
+        return out[:qlen], built
 
-    def iterate(self, query_letters, rounds, min_score=0, pseudocount=10.0, max_evalue=None):
+    def iterate(self, query_letters, rounds, min_score=0, pseudocount=10.0, max_evalue=None, purge_identity=None):
         """Iterated profile search: round 1 scans with the letters; every round builds a PSSM from its reported hits
         (build_pssm), and round r + 1 scans with the one of round r.  Stops after `rounds` rounds, or when a round includes
         the ids the round before included (then the last info has converged = True).  max_evalue: hits go in by their
-        E-value under each round's own fit instead of by min_score (needs set_statistics(True)).
+        E-value under each round's own fit instead of by min_score (needs set_statistics(True)).  purge_identity: build_pssm's,
+        in every round.
         -> (result of the last round, PSSM built from it, list of the rounds' info dicts)"""
         if rounds < 1:
             raise ValueError("rounds must be at least 1")
@@ -959,7 +1053,7 @@ class Driver:
         scoring, infos = None, []
         while True:
             built, info = self.build_pssm(query_letters, result, pssm=scoring, min_score=min_score, pseudocount=pseudocount,
-                                          max_evalue=max_evalue)
+                                          max_evalue=max_evalue, purge_identity=purge_identity)
             info["converged"] = bool(infos) and sorted(info["included"]) == sorted(infos[-1]["included"])
             infos.append(info)
             if len(infos) >= rounds or info["converged"]:

@@ -233,6 +233,33 @@ int swdrv_build_pssm(swdrv* d, const char* master_letters, int32_t qlen, const i
                      const int32_t* scores, int n, int32_t min_score, double pseudocount, int8_t* pssm_out,
                      swdrv_pssm_info* info_out);
 
+/* swdrv_build_pssm with the redundancy filter of sw_msa_filter (include/cudasw4_amd_msa.h) between the
+ * inclusion rule and the weighting: purge_identity P in 1 .. 100 leaves out every hit that is at least P per cent identical
+ * (over its own aligned residues) to the master or to an earlier hit that went in; 0: swdrv_build_pssm.  purged_out
+ * (optional): how many hits that cost; info_out->used and ->included do not count them. */
+int swdrv_build_pssm_purged(swdrv* d, const char* master_letters, int32_t qlen, const int8_t* pssm, const int64_t* ids,
+                            const int32_t* scores, int n, int32_t min_score, double pseudocount, int purge_identity,
+                            int8_t* pssm_out, swdrv_pssm_info* info_out, int32_t* purged_out);
+
+/* The query-anchored multiple alignment of the n hits `ids` / `scores` of a scan of the master: the hits
+ * are aligned as swdrv_align_hits does (pssm non-NULL: as swdrv_align_hits_pssm, the master's letters being the consensus),
+ * and sw_msa_filter runs on what the aligner left on the device.  max_identity: 0 (no filter) or 1 .. 100.
+ * Outputs, each optional: results / cigar as swdrv_align_hits writes them; rows ((n + 1) x qlen bytes, row n the master:
+ * residue codes 0 .. 19, 20 other, 21 gap, 22 none), residues (n + 1), keep (n + 1), purged (1).  out_path non-NULL: the
+ * kept hits are written there as swdrv_write_msa writes them, with the DB's headers and letters and `query_header`. */
+int swdrv_hit_msa(swdrv* d, const char* master_letters, int32_t qlen, const int8_t* pssm, const int64_t* ids,
+                  const int32_t* scores, int n, int max_identity, const char* query_header, const char* out_path, int format,
+                  sw_align_result* results, uint32_t* cigar, int64_t cigar_cap, uint8_t* rows, int32_t* residues, uint8_t* keep,
+                  int32_t* purged);
+
+/* The writer alone (no GPU): '>' + query_header and the master's letters, then for every hit with keep[h] != 0 (keep NULL:
+ * every hit) that is SW_ALIGN_OK with a CIGAR, in the given order, '>' + headers[h] and one line: '-' before q_begin; along
+ * the CIGAR the subject's letter in upper case for '=' / 'X', '-' per 'I' column, the subject's letters in lower case for
+ * 'D' (format 1, FASTA: none); '-' up to the master's length.  format 0: A3M.  results[h].cigar_offset indexes `cigar`. */
+int swdrv_write_msa(const char* path, int format, const char* master_letters, const char* query_header, int n,
+                    const char* const* headers, const char* const* subject_letters, const sw_align_result* results,
+                    const uint32_t* cigar, const uint8_t* keep);
+
 /* The 20 standard columns of a qlen x 21 PSSM as an NCBI ASCII PSSM file (what `align --outPssm` writes and `align --pssm`
  * reads; column 20 is not part of the format).  consensus: qlen residue letters, NUL-terminated.  No GPU needed. */
 int swdrv_write_pssm_ascii(const char* path, const int8_t* pssm, int32_t qlen, const char* consensus);
