@@ -600,6 +600,7 @@ int scan_common(sw_ctx* ctx, const LaunchPlan& lp, const Signals& sg, const int8
     p.chars = chars; p.offsets = offsets; p.lengths = lengths;
     p.positions = positions; p.count_ptr = count_ptr;
     p.first_pos = first_pos; p.n = n;
+    p.len_bound = (max_subject_len + 3) & ~3;   // multi-stripe kernels cut a longer subject here, at a whole letter word
     p.profile = ctx->profiles[kind][shape_index(lanes)][lp.frame].dev;
     p.scores = scores; p.ids = ids; p.id_offset = id_offset;
     p.ovf_pos = ovf_pos; p.ovf_count = ovf_count; p.ovf_check = (ovf_check && kind_packed(kind)) ? 1 : 0;

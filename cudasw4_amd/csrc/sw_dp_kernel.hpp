@@ -395,7 +395,8 @@ struct ScanParams {
     int32_t ovf_check;
     u32* scratch;              // stripe-border spill and address stream: per (workgroup, group) group_region_words(lcap) words
     int32_t lcap;
-    const u32* zeros;          // >= 64 bytes of the kind's zero pattern (border of the first stripe)
+    int32_t len_bound;         // the caller's max_subject_len rounded up to whole letter words (a multiple of 4): multi-stripe kernels take a longer subject's first len_bound residues (lcap is sized from it)
+    const u32* zeros;         // >= 64 bytes of the kind's zero pattern (border of the first stripe)
     u32* work_counter;         // zeroed before the launch: next batch to hand out
     int32_t gex_mag;           // OFFS kernels: a = -gex; then gop holds encode_gap(gop - gex) and the profile s + a
     int32_t renorm_quads;      // OFFS: K/4 — the frame is lowered by a*K every K columns (uniform frame: every K steps; 0: never); a power of two
@@ -1130,6 +1131,13 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
                     r.s1 = p.chars + (p.offsets[r.pos1] - p.offsets[0]);
                 }
             }
+            // a caller that under-reports the longest subject (include/cudasw4_amd.h: max_subject_len): the subject ends at the
+            // bound — its letters (whole words: len_bound is a multiple of 4), its walk and its place in a chain are those
+            // of its first len_bound residues
+            if constexpr (MULTI) {
+                r.len0 = min(r.len0, p.len_bound);
+                r.len1 = min(r.len1, p.len_bound);
+            }
             int lmax = r.len0 > r.len1 ? r.len0 : r.len1;
             if constexpr (LANES <= 16) {  // the 4 (8) groups of a wave run in lock-step
                 if constexpr (LANES <= 4) lmax = max(lmax, __shfl_xor(lmax, 4));
@@ -1150,8 +1158,8 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
         const int8_t* const s1 = pr.s1;
         // the last lane finishes column lmax-1 at step lmax+LANES-2
         int nquads = (pr.lmax + LANES - 1 + 3) >> 2;
-        // the border arrays hold lcap columns (sized from the caller's max_subject_len): never walk past them,
-        // even if a caller under-reports the bound (scores of such subjects are then wrong, memory is not)
+        // the border arrays hold lcap columns (sized from the caller's max_subject_len): never walk past them (load_pair has
+        // cut a longer subject at the bound, so this clamp does not engage: it stays as the last line of defence)
         if constexpr (MULTI) nquads = min(nquads, (p.lcap - 4) >> 2);
         // the same in every lane of the wave (lmax was reduced over its groups): saying so turns the quad loop, its
         // letter-reload test and the frame-lowering segments into scalar control flow (the counter otherwise lives in a

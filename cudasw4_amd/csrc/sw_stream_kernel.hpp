@@ -106,6 +106,9 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
     const u32 zstart = A::level_word(p.level_base + a * (LANES - lane));
     const u32 zbefore = A::level_word(p.level_base + a * (LANES - lane - 1));
     const int smax = min(max(p.stream_slots, 1), kStreamMaxSlots);
+    // a caller that under-reports the longest subject (include/cudasw4_amd.h: max_subject_len): multi-stripe launches, whose
+    // border scratch is sized from the bound, take a longer subject's first len_bound residues (as sw_scan_kernel does)
+    auto bounded = [&](int len) { return MULTI ? min(len, p.len_bound) : len; };
 
     for (;;) {
         // ---- a round: as many batches as the budgets allow while plenty are left (guided self-scheduling), longest first
@@ -123,7 +126,7 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
             const int batch = nbatches - 1 - (cur + k);
             const bool in = k < want && batch >= 0;
             int w = 0;
-            if (in) w = max(p.lengths[p.first_pos + min(n - 1, batch * kSubjPerBatch + kSubjPerBatch - 1)] + (k > 0 ? 1 : 0), kMinWidth);
+            if (in) w = max(bounded(p.lengths[p.first_pos + min(n - 1, batch * kSubjPerBatch + kSubjPerBatch - 1)]) + (k > 0 ? 1 : 0), kMinWidth);
             int c = w;
 #pragma unroll
             for (int d = 1; d < LANES; d <<= 1) {
@@ -158,8 +161,8 @@ __global__ void __launch_bounds__(kThreads, (min_waves<KIND, R, LANES, MULTI>())
             if (lane < S) {
                 const int batch = nbatches - 1 - (b0 + lane);
                 const int i0 = batch * kSubjPerBatch + group * 2;
-                if (i0 < n) { slen0 = p.lengths[p.first_pos + i0]; soff0 = (u32)((p.offsets[p.first_pos + i0] - p.offsets[0]) >> 2); }
-                if (i0 + 1 < n) { slen1 = p.lengths[p.first_pos + i0 + 1]; soff1 = (u32)((p.offsets[p.first_pos + i0 + 1] - p.offsets[0]) >> 2); }
+                if (i0 < n) { slen0 = bounded(p.lengths[p.first_pos + i0]); soff0 = (u32)((p.offsets[p.first_pos + i0] - p.offsets[0]) >> 2); }
+                if (i0 + 1 < n) { slen1 = bounded(p.lengths[p.first_pos + i0 + 1]); soff1 = (u32)((p.offsets[p.first_pos + i0 + 1] - p.offsets[0]) >> 2); }
             }
             slens = (u32)slen0 | ((u32)slen1 << 16);
             int lmax = max(slen0, slen1);

@@ -116,11 +116,12 @@ size_t sw_scan_temp_bytes(sw_ctx* ctx, int kind, int part_id, int32_t n, int32_t
  *                   counting PositionsIterator, kernels.cuh:28)
  *   max_subject_len upper bound of lengths[first_pos .. first_pos+n).  CONTRACT: it sizes the stripe-border scratch of
  *                   multi-stripe queries (sw_scan_temp_bytes) and the kernels never walk past that scratch, so an
- *                   under-reported bound is memory-safe but SILENTLY truncates longer subjects at the bound (their
- *                   scores are then those of the truncated subject).  In a launch that walks chains of subject pairs
- *                   (sw_scan_temp_bytes) the bound also places the pairs of a chain: under-reported, the scores of the
- *                   OTHER subjects of a truncated subject's chain (up to CUDASW4_AMD_CHAIN x 32 neighbours in the range) are
- *                   undefined too.  Pass the true maximum (the reference passes the
+ *                   under-reported bound is memory-safe but SILENTLY truncates longer subjects at the bound: a
+ *                   multi-stripe launch reads a longer subject's length as the bound rounded up to a multiple of 4 (a
+ *                   whole letter word), and its score is that of the subject cut there.  The other subjects keep their
+ *                   scores, in a launch that walks chains of subject pairs (sw_scan_temp_bytes) too: a pair takes its
+ *                   place in the chain by its cut length.  (Only multi-stripe launches cut: a single-stripe launch has no
+ *                   such scratch.)  Pass the true maximum (the reference passes the
  *                   partition's boundary, cudasw4.cuh:1767-1912); over-reporting only costs scratch.
  *                   Debugging a binding: with CUDASW4_AMD_CHECK_BOUNDS=1 in the environment of sw_ctx_create every scan
  *                   and re-score first finds the longest subject of its range on the device (one small kernel and a
@@ -133,7 +134,10 @@ size_t sw_scan_temp_bytes(sw_ctx* ctx, int kind, int part_id, int32_t n, int32_t
  *                   The list may hold a few subjects more than strictly overflowed: the kernels keep
  *                   column j's values raised by |gex|*(j+16) and flag a subject as soon as the bound
  *                   score + |gex|*(min(columns,K)+36) reaches the limit (never one scoring below limit-1536
- *                   for F16X2 / limit-2100 for I16X2 with gex = -1).  Re-scoring them all keeps every score exact.
+ *                   for F16X2 / limit-2100 for I16X2 with gex = -1).  A launch that streams short subjects through the
+ *                   lanes back to back (csrc/sw_stream_kernel.hpp) also lists the subject that follows one scoring 508
+ *                   (F16X2) / 2044 (I16X2) or more in its lanes, and the one behind that while what is left there may
+ *                   still be high (SW_BATCH_CNT_DIRTY counts them).  Re-scoring them all keeps every score exact.
  *   temp            DEVICE scratch of at least sw_scan_temp_bytes() (may be NULL when that is 0)
  */
 int sw_scan_partition(sw_ctx* ctx, int kind, int part_id,
