@@ -51,6 +51,10 @@ MASK_EXPORTS = ["sw_mask_subjects", "sw_mask_subjects_phases"]
 # ... and include/cudasw4_amd_msa.h (the query-anchored MSA of a query's hits and its redundancy filter)
 MSA_EXPORTS = ["sw_msa_filter"]
 MSA_GAP, MSA_NONE, MSA_MAX_HITS = 21, 22, 1 << 15
+# ... and include/cudasw4_amd_msa_select.h (coverage, identity to the query and the diversity selection over those rows)
+MSA_SELECT_EXPORTS = ["sw_msa_select"]
+MSA_SELECT_MAX_HITS, MSA_SELECT_MAX_LADDER = 1 << 14, 16
+MSA_STATE_NONE, MSA_STATE_KEPT, MSA_STATE_COVERAGE, MSA_STATE_QUERY_IDENTITY, MSA_STATE_THINNED = 0, 1, 2, 3, 4
 
 
 # sw_align_hits (include/cudasw4_amd.h): result records, statuses, flags, CIGAR op codes
@@ -442,6 +446,46 @@ def msa_filter(ctx, query, qlen, n, chars, offsets, lengths, results, cigar, inc
                  include or None, max_identity, rows or None, residues or None, keep or None, purged or None, pair_ident or None,
                  temp or None, temp_bytes, ctypes.pointer(need), ctypes.cast(ev, ctypes.c_void_p) if ev is not None else None,
                  stream or None)
+    check(f(ctx.handle if ctx is not None else None, ctypes.byref(a)))
+    return int(need.value)
+
+
+class _MsaSelectArgs(ctypes.Structure):
+    _fields_ = [("query", ctypes.c_void_p), ("qlen", ctypes.c_int32), ("n", ctypes.c_int32), ("chars", ctypes.c_void_p),
+                ("offsets", ctypes.c_void_p), ("lengths", ctypes.c_void_p), ("results", ctypes.c_void_p),
+                ("cigar", ctypes.c_void_p), ("include", ctypes.c_void_p), ("min_coverage", ctypes.c_int32),
+                ("min_query_identity", ctypes.c_int32), ("diff", ctypes.c_int32), ("ladder", ctypes.POINTER(ctypes.c_int32)),
+                ("n_ladder", ctypes.c_int32), ("state", ctypes.c_void_p), ("residues", ctypes.c_void_p),
+                ("counts", ctypes.c_void_p), ("depth", ctypes.c_void_p), ("rows", ctypes.c_void_p), ("levels", ctypes.c_void_p),
+                ("temp", ctypes.c_void_p), ("temp_bytes", ctypes.c_size_t),
+                ("temp_bytes_needed", ctypes.POINTER(ctypes.c_size_t)), ("phase_events", ctypes.c_void_p),
+                ("stream", ctypes.c_void_p)]
+
+
+def msa_select(ctx, query, qlen, n, chars, offsets, lengths, results, cigar, include, min_coverage, min_query_identity, diff,
+               ladder, state, residues, counts, depth=0, rows=0, levels=0, temp=0, temp_bytes=0, stream=0, phase_events=None):
+    """sw_msa_select (include/cudasw4_amd_msa_select.h): the state of every row of the query-anchored alignment (uint8, n + 1:
+    0 none, 1 kept, 2 below min_coverage, 3 below min_query_identity, 4 thinned) under the diversity selection `diff` over the
+    identity `ladder` (a host sequence of 1 .. 16 strictly ascending rungs in 1 .. 100), the residue counts (int32, n + 1),
+    counts (int32, 4: kept hits, below coverage, below query identity, thinned) and optionally depth (int32, qlen), rows
+    (uint8, (n + 1) x qlen) and, for tests, levels (uint8, (n + 1) x (n + 1)).  Every buffer is a device pointer as an
+    integer; query, include, depth, rows and levels may be 0.  Asynchronous on `stream`.  phase_events: 4 hipEvent_t handles
+    or None.  -> the temp bytes the call needs; with temp == 0 nothing is launched."""
+    if not hasattr(lib, "sw_msa_select"):
+        raise SwError(-1, "this build of libcudasw4_amd.so has no sw_msa_select")
+    f = lib.sw_msa_select
+    if f.argtypes is None:   # bound on first use (CUDASW4_AMD_LIB may name an older build)
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(_MsaSelectArgs)]
+    ev = (ctypes.c_void_p * 4)(*phase_events) if phase_events is not None else None
+    rungs = [int(x) for x in ladder] if ladder is not None else []
+    lad = (ctypes.c_int32 * max(len(rungs), 1))(*rungs)
+    need = ctypes.c_size_t(0)
+    a = _MsaSelectArgs(query or None, qlen, n, chars or None, offsets or None, lengths or None, results or None, cigar or None,
+                       include or None, min_coverage, min_query_identity, diff,
+                       ctypes.cast(lad, ctypes.POINTER(ctypes.c_int32)) if ladder is not None else None, len(rungs),
+                       state or None, residues or None, counts or None, depth or None, rows or None, levels or None,
+                       temp or None, temp_bytes, ctypes.pointer(need),
+                       ctypes.cast(ev, ctypes.c_void_p) if ev is not None else None, stream or None)
     check(f(ctx.handle if ctx is not None else None, ctypes.byref(a)))
     return int(need.value)
 

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../../include/cudasw4_amd_msa.h"
+#include "../../../include/cudasw4_amd_msa_select.h"
 #include "cli_options.hpp"
 #include "db_format.hpp"
 #include "hit_alignment.hpp"
@@ -214,7 +215,19 @@ struct MsaOutput {
         }
         std::vector<uint8_t> keep(n, 0);
         int32_t purged = 0;
-        if (n > 0) {
+        int32_t counts[4] = {0, 0, 0, 0};
+        if (o.selectsMsaRows()) {
+            if (n > 0) {
+                MsaSelectParams params;
+                params.minCoverage = o.msaMinCoverage;
+                params.minQueryIdentity = o.msaMinQueryIdentity;
+                params.diff = o.msaDiff;
+                params.ladder = o.msaLadder;
+                const MsaSelectResult f = msa->select(master.data(), qlen, shown.data(), params, false);
+                for (size_t i = 0; i < n; i++) keep[i] = f.state[i] == SW_MSA_STATE_KEPT;
+                std::copy(f.counts, f.counts + 4, counts);
+            }
+        } else if (n > 0) {
             const MsaFilterResult f = msa->filter(master.data(), qlen, shown.data(), o.msaMaxIdentity, false);
             keep.assign(f.keep.begin(), f.keep.begin() + long(n));
             purged = f.purged;
@@ -231,7 +244,10 @@ struct MsaOutput {
         std::string header(queryHeader);
         if (!header.empty() && header[0] == '>') header.erase(0, 1);
         const size_t written = write_msa(path, format, master, header, headers, letters, *alignments, keep.data());
-        if (o.verbose)
+        if (o.verbose && o.selectsMsaRows())
+            std::cout << "msa: " << written << " of " << reported << " results written, " << counts[1] << " below coverage, " << counts[2]
+                      << " below query identity, " << counts[3] << " thinned, " << noTrace << " without a trace\n";
+        else if (o.verbose)
             std::cout << "msa: " << written << " of " << reported << " results written, " << purged << " purged, " << noTrace
                       << " without a trace\n";
     }
@@ -539,12 +555,52 @@ int main(int argc, char** argv) {
             };
             if ((options.haveMsaFormat || options.haveMsaMaxIdentity) && !options.haveOutMsa)
                 throw std::runtime_error("--msaFormat / --msaMaxIdentity need --outMsa PREFIX: they say how the multiple alignment is written");
+            if (options.selectsMsaRows() && !options.haveOutMsa)
+                throw std::runtime_error("--msaMinCoverage / --msaMinQueryIdentity / --msaDiff / --msaDiffLadder need --outMsa PREFIX: they say which results the multiple alignment keeps");
             if (options.haveOutMsa && options.outMsa.empty()) throw std::runtime_error("--outMsa needs a file prefix");
             MsaFormat format;
             if (!parse_msa_format(options.msaFormat, format))
                 throw std::runtime_error("--msaFormat must be a3m or fasta, not '" + options.msaFormat + "'");
             if (options.haveMsaMaxIdentity) options.msaMaxIdentity = percent(options.msaMaxIdentityText, "--msaMaxIdentity");
             if (options.havePurgeIdentity) options.purgeIdentity = percent(options.purgeIdentityText, "--purgeIdentity");
+            if (options.haveMsaMinCoverage) options.msaMinCoverage = percent(options.msaMinCoverageText, "--msaMinCoverage");
+            if (options.haveMsaMinQueryIdentity) options.msaMinQueryIdentity = percent(options.msaMinQueryIdentityText, "--msaMinQueryIdentity");
+            if (options.haveMsaDiff) {
+                const std::string& text = options.msaDiffText;
+                size_t used = 0;
+                long v = 0;
+                try { v = std::stol(text, &used); } catch (...) { used = 0; }
+                if (text.empty() || used != text.size() || v < 1 || v > INT32_MAX)
+                    throw std::runtime_error("--msaDiff must be an integer of at least 1, not '" + text + "'");
+                options.msaDiff = int(v);
+            }
+            if (options.haveMsaDiffLadder) {
+                if (!options.haveMsaDiff) throw std::runtime_error("--msaDiffLadder needs --msaDiff D: it names the rungs of the diversity selection");
+                if (options.haveMsaMaxIdentity)
+                    throw std::runtime_error("--msaDiffLadder cannot be combined with --msaMaxIdentity: the ladder's last rung is the identity cut");
+                const std::string& text = options.msaDiffLadderText;
+                const std::string bad = "--msaDiffLadder must be 1 .. 16 strictly ascending integers in 1 .. 100 separated by commas, not '" + text + "'";
+                for (size_t at = 0; at <= text.size();) {
+                    const size_t comma = std::min(text.find(',', at), text.size());
+                    const std::string part = text.substr(at, comma - at);
+                    size_t used = 0;
+                    long v = 0;
+                    try { v = std::stol(part, &used); } catch (...) { used = 0; }
+                    if (part.empty() || used != part.size() || v < 1 || v > 100) throw std::runtime_error(bad);
+                    if (!options.msaLadder.empty() && v <= options.msaLadder.back()) throw std::runtime_error(bad);
+                    options.msaLadder.push_back(int32_t(v));
+                    at = comma + 1;
+                }
+                if (options.msaLadder.size() > SW_MSA_SELECT_MAX_LADDER) throw std::runtime_error(bad);
+            } else if (options.haveMsaDiff) {   // 20, 30, ... below P, then P
+                const int last = options.haveMsaMaxIdentity ? options.msaMaxIdentity : 90;
+                for (int rung = 20; rung < last; rung += 10) options.msaLadder.push_back(rung);
+                options.msaLadder.push_back(last);
+            } else if (options.selectsMsaRows()) {
+                // coverage / query identity alone: the weakest cut the selection has (a result whose every residue repeats a
+                // written row), unless --msaMaxIdentity names one
+                options.msaLadder.push_back(options.haveMsaMaxIdentity ? options.msaMaxIdentity : 100);
+            }
             if (options.havePurgeIdentity && !options.buildsPssm())
                 throw std::runtime_error("--purgeIdentity needs --iterations above 1 or --outPssm: it says which results go into the PSSM");
             if ((options.haveOutMsa || options.havePurgeIdentity) && options.interactive)
@@ -553,6 +609,8 @@ int main(int argc, char** argv) {
                 throw std::runtime_error("--outMsa needs --top of at least 1: the alignment is made of the reported results");
             if (options.haveOutMsa && options.numTopOutputs > SW_MSA_MAX_HITS)
                 throw std::runtime_error("--outMsa takes --top up to " + std::to_string(SW_MSA_MAX_HITS));
+            if (options.selectsMsaRows() && options.numTopOutputs > SW_MSA_SELECT_MAX_HITS)
+                throw std::runtime_error("--msaMinCoverage / --msaMinQueryIdentity / --msaDiff take --top up to " + std::to_string(SW_MSA_SELECT_MAX_HITS));
         }
         if ((options.haveMaskWindow || options.haveMaskTrigger || options.haveMaskExtend) && !options.maskSubjects)
             throw std::runtime_error("--maskWindow / --maskTrigger / --maskExtend need --maskSubjects: they say how the subjects are masked");

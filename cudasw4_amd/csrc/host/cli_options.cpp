@@ -55,6 +55,10 @@ void printOptions(const ProgramOptions& o) {
     if (o.haveOutMsa) std::cout << "outMsa: " << o.outMsa << "\n";
     if (o.haveMsaFormat) std::cout << "msaFormat: " << o.msaFormat << "\n";
     if (o.haveMsaMaxIdentity) std::cout << "msaMaxIdentity: " << o.msaMaxIdentityText << "\n";
+    if (o.haveMsaMinCoverage) std::cout << "msaMinCoverage: " << o.msaMinCoverageText << "\n";
+    if (o.haveMsaMinQueryIdentity) std::cout << "msaMinQueryIdentity: " << o.msaMinQueryIdentityText << "\n";
+    if (o.haveMsaDiff) std::cout << "msaDiff: " << o.msaDiffText << "\n";
+    if (o.haveMsaDiffLadder) std::cout << "msaDiffLadder: " << o.msaDiffLadderText << "\n";
     std::cout << "blosum: " << substitution_matrix(o.matrix).name << "\n";
     std::cout << "singlePassType: " << to_string(o.kernels.singlePassType) << "\n";
     std::cout << "manyPassType_small: " << to_string(o.kernels.manyPassType_small) << "\n";
@@ -115,6 +119,10 @@ bool parseArgs(int argc, char** argv, ProgramOptions& o) {
         else if (arg == "--outMsa") { o.outMsa = value(i); o.haveOutMsa = true; }
         else if (arg == "--msaFormat") { o.msaFormat = value(i); o.haveMsaFormat = true; }
         else if (arg == "--msaMaxIdentity") { o.msaMaxIdentityText = value(i); o.haveMsaMaxIdentity = true; }
+        else if (arg == "--msaMinCoverage") { o.msaMinCoverageText = value(i); o.haveMsaMinCoverage = true; }
+        else if (arg == "--msaMinQueryIdentity") { o.msaMinQueryIdentityText = value(i); o.haveMsaMinQueryIdentity = true; }
+        else if (arg == "--msaDiff") { o.msaDiffText = value(i); o.haveMsaDiff = true; }
+        else if (arg == "--msaDiffLadder") { o.msaDiffLadderText = value(i); o.haveMsaDiffLadder = true; }
         else if (arg == "--printLengthPartitions") o.printLengthPartitions = true;
         else if (arg == "--prefetchDBFile") o.prefetchDBFile = true;
         else if (arg == "--top") o.numTopOutputs = std::atoi(value(i).c_str());
@@ -197,7 +205,16 @@ void printHelp(char** argv) {
     std::cout << "      --msaFormat a3m|fasta : a3m (default): insertions relative to the query in lower case. fasta: insertions left out, every\n"
                  "        line as long as the query; the file is PREFIX.<query number>.fasta. Needs --outMsa\n";
     std::cout << "      --msaMaxIdentity P : Write only results that are less than P per cent identical to the query and to every result written\n"
-                 "        before them (P in 1 .. 100, a greedy filter on the GPU). Needs --outMsa. Default: every aligned result is written\n\n";
+                 "        before them (P in 1 .. 100, a greedy filter on the GPU). Needs --outMsa. Default: every aligned result is written\n";
+    std::cout << "      --msaMinCoverage C : Write only results that align at least C per cent of the query's positions (C in 1 .. 100). Needs --outMsa\n";
+    std::cout << "      --msaMinQueryIdentity Q : Write only results of whose aligned residues at least Q per cent equal the query's (Q in 1 .. 100).\n"
+                 "        Needs --outMsa\n";
+    std::cout << "      --msaDiff D : Write the most diverse results that leave at least D residues in every column where so many exist (D >= 1): the\n"
+                 "        results are taken rung by rung of a rising identity ladder, each only while one of its columns has fewer than D\n"
+                 "        residues and no written row is similar to it at the rung. Rungs: 20, 30, ... below --msaMaxIdentity (default 90),\n"
+                 "        then that. At most --top 16384. Needs --outMsa\n";
+    std::cout << "      --msaDiffLadder p0,p1,... : The rungs of --msaDiff: 1 .. 16 strictly ascending values in 1 .. 100; the last one is the identity cut,\n"
+                 "        so --msaMaxIdentity cannot be given with it. Needs --msaDiff\n\n";
     std::cout << "   Search statistics\n";
     std::cout << "      --evalues : Report a Z-score and an E-value with every result: the scores of the whole scan are regressed on the\n"
                  "        logarithm of the subject length (as FASTA / SSEARCH do), fitted per query on the GPU's score histogram. Two more TSV\n"

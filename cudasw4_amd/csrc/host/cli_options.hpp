@@ -82,6 +82,14 @@ struct ProgramOptions {
     std::string msaFormat = "a3m", msaMaxIdentityText, purgeIdentityText;
     int msaMaxIdentity = 0, purgeIdentity = 0;
     bool writesMsa() const { return haveOutMsa; }
+    // The selection of the rows that are written (an extension): --msaMinCoverage C, --msaMinQueryIdentity Q,
+    // --msaDiff D and --msaDiffLadder p0,p1,...  Kept as given and checked in main, before any device is opened, which
+    // fills the numbers and the ladder.  With any of them the file is written from sw_msa_select's states.
+    bool haveMsaMinCoverage = false, haveMsaMinQueryIdentity = false, haveMsaDiff = false, haveMsaDiffLadder = false;
+    std::string msaMinCoverageText, msaMinQueryIdentityText, msaDiffText, msaDiffLadderText;
+    int msaMinCoverage = 0, msaMinQueryIdentity = 0, msaDiff = 0;
+    std::vector<int32_t> msaLadder;
+    bool selectsMsaRows() const { return haveMsaMinCoverage || haveMsaMinQueryIdentity || haveMsaDiff || haveMsaDiffLadder; }
     bool prefetchDBFile = false;
     int numTopOutputs = 10;
     int gop = -11;

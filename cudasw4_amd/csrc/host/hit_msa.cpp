@@ -13,6 +13,7 @@
 
 #include "../../../include/cudasw4_amd_driver.h"
 #include "../../../include/cudasw4_amd_msa.h"
+#include "../../../include/cudasw4_amd_msa_select.h"
 #include "driver_handle.hpp"
 #include "sequence_codec.hpp"
 
@@ -92,6 +93,68 @@ MsaFilterResult HitMsa::filter(const char* master, int32_t qlen, const uint8_t* 
     hip_check(hipMemcpyAsync(out.keep.data(), a.keep, n + 1, hipMemcpyDeviceToHost, res.stream), "hipMemcpyAsync");
     hip_check(hipMemcpyAsync(out.residues.data(), a.residues, (n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, res.stream), "hipMemcpyAsync");
     hip_check(hipMemcpyAsync(&out.purged, a.purged, sizeof(int32_t), hipMemcpyDeviceToHost, res.stream), "hipMemcpyAsync");
+    if (wantRows) hip_check(hipMemcpyAsync(out.rows.data(), a.rows, rowBytes, hipMemcpyDeviceToHost, res.stream), "hipMemcpyAsync");
+    hip_check(hipStreamSynchronize(res.stream), "hipStreamSynchronize");
+    return out;
+}
+
+MsaSelectResult HitMsa::select(const char* master, int32_t qlen, const uint8_t* include, const MsaSelectParams& params, bool wantRows) {
+    if (qlen < 1) throw std::runtime_error("MSA: empty query");
+    const HitAligner::Resident res = aligner_.resident();
+    if (res.n > size_t(SW_MSA_SELECT_MAX_HITS))
+        throw std::runtime_error("MSA: the selection takes at most " + std::to_string(SW_MSA_SELECT_MAX_HITS) + " hits");
+    if (!res.ctx) throw std::runtime_error("MSA: the hits have not been aligned");
+    const size_t n = res.n;
+    device_ = res.device;
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    sw_msa_select_args a{};
+    if (master) {
+        std::vector<int8_t> codes(static_cast<size_t>(qlen));
+        for (int32_t i = 0; i < qlen; i++) codes[size_t(i)] = encode_residue(master[i]);
+        void* dMaster = grow(kMaster, size_t(qlen));
+        hip_check(hipMemcpyAsync(dMaster, codes.data(), size_t(qlen), hipMemcpyHostToDevice, res.stream), "hipMemcpyAsync");
+        hip_check(hipStreamSynchronize(res.stream), "hipStreamSynchronize");   // (codes leaves scope)
+        a.query = static_cast<const int8_t*>(dMaster);
+    }
+    a.qlen = qlen;
+    a.n = int32_t(n);
+    a.chars = res.chars;
+    a.offsets = res.offsets;
+    a.lengths = res.lengths;
+    a.results = res.results;
+    a.cigar = res.cigar;
+    if (include && n > 0) {
+        void* dInclude = grow(kInclude, n);
+        hip_check(hipMemcpyAsync(dInclude, include, n, hipMemcpyHostToDevice, res.stream), "hipMemcpyAsync");
+        a.include = static_cast<const uint8_t*>(dInclude);
+    }
+    a.min_coverage = params.minCoverage;
+    a.min_query_identity = params.minQueryIdentity;
+    a.diff = params.diff;
+    a.ladder = params.ladder.data();
+    a.n_ladder = int32_t(params.ladder.size());
+    const size_t rowBytes = (n + 1) * size_t(qlen);
+    if (wantRows) a.rows = static_cast<uint8_t*>(grow(kRows, rowBytes));
+    a.residues = static_cast<int32_t*>(grow(kResidues, (n + 1) * sizeof(int32_t)));
+    a.state = static_cast<uint8_t*>(grow(kState, n + 1));
+    a.counts = static_cast<int32_t*>(grow(kCounts, 4 * sizeof(int32_t)));
+    a.depth = static_cast<int32_t*>(grow(kDepth, size_t(qlen) * sizeof(int32_t)));
+    a.stream = res.stream;
+    size_t need = 0;
+    a.temp_bytes_needed = &need;
+    if (sw_msa_select(res.ctx, &a) != SW_OK) throw std::runtime_error(std::string("MSA: sw_msa_select: ") + sw_last_error());
+    a.temp = grow(kTemp, need);
+    a.temp_bytes = cap_[kTemp];
+    if (sw_msa_select(res.ctx, &a) != SW_OK) throw std::runtime_error(std::string("MSA: sw_msa_select: ") + sw_last_error());
+    MsaSelectResult out;
+    out.state.resize(n + 1);
+    out.residues.resize(n + 1);
+    out.depth.resize(size_t(qlen));
+    if (wantRows) out.rows.resize(rowBytes);
+    hip_check(hipMemcpyAsync(out.state.data(), a.state, n + 1, hipMemcpyDeviceToHost, res.stream), "hipMemcpyAsync");
+    hip_check(hipMemcpyAsync(out.residues.data(), a.residues, (n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, res.stream), "hipMemcpyAsync");
+    hip_check(hipMemcpyAsync(out.counts, a.counts, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, res.stream), "hipMemcpyAsync");
+    hip_check(hipMemcpyAsync(out.depth.data(), a.depth, size_t(qlen) * sizeof(int32_t), hipMemcpyDeviceToHost, res.stream), "hipMemcpyAsync");
     if (wantRows) hip_check(hipMemcpyAsync(out.rows.data(), a.rows, rowBytes, hipMemcpyDeviceToHost, res.stream), "hipMemcpyAsync");
     hip_check(hipStreamSynchronize(res.stream), "hipStreamSynchronize");
     return out;
@@ -239,6 +302,76 @@ extern "C" int swdrv_hit_msa(swdrv* d, const char* master_letters, int32_t qlen,
             }
             swh::write_msa(std::string(out_path), format == 0 ? swh::MsaFormat::A3m : swh::MsaFormat::Fasta,
                            std::string(master_letters, size_t(qlen)), query_header ? query_header : "query", hs, ss, hits, f.keep.data());
+        }
+        return 0;
+    } catch (const std::exception& e) {
+        swh::set_driver_error(e.what());
+        return -1;
+    }
+}
+
+extern "C" int swdrv_hit_msa_select(swdrv* d, const char* master_letters, int32_t qlen, const int8_t* pssm, const int64_t* ids,
+                                    const int32_t* scores, int n, int min_coverage, int min_query_identity, int diff,
+                                    const int32_t* ladder, int n_ladder, const char* query_header, const char* out_path, int format,
+                                    sw_align_result* results, uint32_t* cigar, int64_t cigar_cap, uint8_t* rows, int32_t* residues,
+                                    uint8_t* state, int32_t* depth, int32_t* counts) {
+    try {
+        if (!d || !d->driver) throw std::runtime_error("null driver");
+        if (!master_letters || qlen < 1 || n < 0 || (n > 0 && (!ids || !scores))) throw std::runtime_error("MSA: bad arguments");
+        if (format != 0 && format != 1) throw std::runtime_error("MSA: format must be 0 (a3m) or 1 (fasta)");
+        if (!ladder || n_ladder < 1 || n_ladder > SW_MSA_SELECT_MAX_LADDER) throw std::runtime_error("MSA: the ladder needs 1 .. 16 rungs");
+        swh::MsaSelectParams params;
+        params.minCoverage = min_coverage;
+        params.minQueryIdentity = min_query_identity;
+        params.diff = diff;
+        params.ladder.assign(ladder, ladder + n_ladder);
+        swh::HitAligner aligner(*d->driver);
+        std::vector<swh::HitAlignment> hits;
+        if (n > 0)
+            hits = pssm ? aligner.align(pssm, qlen, master_letters, ids, scores, size_t(n)) : aligner.align(master_letters, qlen, ids, scores, size_t(n));
+        swh::MsaSelectResult f;
+        if (n > 0) {
+            swh::HitMsa msa(aligner);
+            f = msa.select(master_letters, qlen, nullptr, params, rows != nullptr);
+        } else {   // (no align() call behind an empty list: the master alone)
+            f.state.assign(1, 0);
+            f.residues.assign(1, 0);
+            f.depth.assign(size_t(qlen), 0);
+            for (int32_t i = 0; i < qlen; i++) f.depth[size_t(i)] = swh::encode_residue(master_letters[i]) < 20;
+            for (int32_t i = 0; i < qlen; i++) f.residues[0] += f.depth[size_t(i)];
+            f.state[0] = f.residues[0] > 0;
+            if (!f.state[0]) f.depth.assign(size_t(qlen), 0);
+            if (rows)
+                for (int32_t i = 0; i < qlen; i++) rows[i] = uint8_t(std::min<int>(swh::encode_residue(master_letters[i]), 20));
+        }
+        int64_t used = 0;
+        for (size_t i = 0; i < hits.size(); i++) {
+            if (results) {
+                results[i] = hits[i].r;
+                results[i].cigar_offset = used;
+            }
+            if (cigar) {
+                if (used + int64_t(hits[i].cigar.size()) > cigar_cap) throw std::runtime_error("cigar_cap too small");
+                std::copy(hits[i].cigar.begin(), hits[i].cigar.end(), cigar + used);
+            }
+            used += int64_t(hits[i].cigar.size());
+        }
+        if (rows && n > 0) std::copy(f.rows.begin(), f.rows.end(), rows);
+        if (residues) std::copy(f.residues.begin(), f.residues.end(), residues);
+        if (state) std::copy(f.state.begin(), f.state.end(), state);
+        if (depth) std::copy(f.depth.begin(), f.depth.end(), depth);
+        if (counts) std::copy(f.counts, f.counts + 4, counts);
+        if (out_path) {
+            const size_t count = static_cast<size_t>(n);
+            std::vector<std::string> hs(count), ss(count);
+            std::vector<uint8_t> keep(count + 1, 0);
+            for (int h = 0; h < n; h++) {
+                hs[size_t(h)] = std::string(d->driver->getReferenceHeader(ids[h]));
+                ss[size_t(h)] = d->driver->getReferenceSequence(ids[h]);
+                keep[size_t(h)] = f.state[size_t(h)] == SW_MSA_STATE_KEPT;
+            }
+            swh::write_msa(std::string(out_path), format == 0 ? swh::MsaFormat::A3m : swh::MsaFormat::Fasta,
+                           std::string(master_letters, size_t(qlen)), query_header ? query_header : "query", hs, ss, hits, keep.data());
         }
         return 0;
     } catch (const std::exception& e) {

@@ -19,7 +19,23 @@ struct MsaFilterResult {
     std::vector<uint8_t> rows;        // (n + 1) x qlen when asked for, else empty
 };
 
-// Runs sw_msa_filter on HitAligner::resident(): the aligner's device, context and stream, buffers of its own that grow on
+// The selection of DESIGN.md §18 (sw_msa_select, include/cudasw4_amd_msa_select.h): 0 switches a test off.
+struct MsaSelectParams {
+    int minCoverage = 0;              // C: per cent of the query's positions a hit must have aligned
+    int minQueryIdentity = 0;         // Q: per cent of a hit's residues that must equal the master's
+    int diff = 0;                     // D: a hit is kept only while some column of it has fewer than D kept residues
+    std::vector<int32_t> ladder{90};  // strictly ascending identity thresholds, 1 .. 16 values in 1 .. 100
+};
+
+struct MsaSelectResult {
+    std::vector<uint8_t> state;       // n + 1 (SW_MSA_STATE_*), entry n the master's
+    std::vector<int32_t> residues;    // n + 1
+    int32_t counts[4] = {0, 0, 0, 0};  // kept hits, below coverage, below query identity, thinned
+    std::vector<int32_t> depth;       // qlen
+    std::vector<uint8_t> rows;        // (n + 1) x qlen when asked for, else empty
+};
+
+// Runs sw_msa_filter / sw_msa_select on HitAligner::resident(): the aligner's device, context and stream, buffers of its own that grow on
 // demand.  Valid between an align() and the next one.
 class HitMsa {
 public:
@@ -31,12 +47,14 @@ public:
     // master: qlen residue letters (encode_residue; nullptr: no master row).  include: nullptr or one byte per resident hit.
     // maxIdentity: 0 (no filter) or 1 .. 100.
     MsaFilterResult filter(const char* master, int32_t qlen, const uint8_t* include, int maxIdentity, bool wantRows);
+    // the same inputs through sw_msa_select; at most SW_MSA_SELECT_MAX_HITS resident hits
+    MsaSelectResult select(const char* master, int32_t qlen, const uint8_t* include, const MsaSelectParams& params, bool wantRows);
 
 private:
     void* grow(int slot, size_t bytes);
     HitAligner& aligner_;
     int device_ = -1;
-    enum { kMaster, kInclude, kRows, kResidues, kKeep, kPurged, kTemp, kBuffers };
+    enum { kMaster, kInclude, kRows, kResidues, kKeep, kPurged, kTemp, kState, kCounts, kDepth, kBuffers };
     void* buf_[kBuffers] = {};
     size_t cap_[kBuffers] = {};
 };

@@ -25,7 +25,7 @@ EXPORTS = ["swdrv_last_error", "swdrv_create", "swdrv_destroy", "swdrv_open_db",
            "swdrv_tail_overlaps", "swdrv_prefers_two_in_flight", "swdrv_pipeline_launches", "swdrv_handshake_active", "swdrv_preferred_in_flight",
            "swdrv_latency_scans", "swdrv_plan_runs_mode", "swdrv_align_hits", "swdrv_scan_pssm", "swdrv_scan_submit_pssm",
            "swdrv_align_hits_pssm", "swdrv_align_hsps", "swdrv_align_hsps_pssm", "swdrv_pssm_from_counts", "swdrv_build_pssm", "swdrv_write_pssm_ascii",
-           "swdrv_build_pssm_purged", "swdrv_hit_msa", "swdrv_write_msa",
+           "swdrv_build_pssm_purged", "swdrv_hit_msa", "swdrv_hit_msa_select", "swdrv_write_msa",
            "swdrv_set_statistics", "swdrv_last_statistics", "swdrv_stats_from_histogram", "swdrv_evalues", "swdrv_length_bin",
            "swdrv_set_ranking", "swdrv_last_ranking", "swdrv_zscore_for_evalue", "swdrv_rank_order",
            "swdrv_calibrate_shuffled", "swdrv_calibrate_shuffled_pssm", "swdrv_set_rank_fit", "swdrv_shuffle_sample",
@@ -219,6 +219,15 @@ def _msa_fns():
                        ctypes.POINTER(ctypes.c_int32)]
         wr.argtypes = [cp, i, cp, cp, i, ctypes.POINTER(cp), ctypes.POINTER(cp), vp, vp, vp]
     return bp, hm, wr
+
+
+def _msa_select_fn():
+    """swdrv_hit_msa_select, bound on first use"""
+    f = lib.swdrv_hit_msa_select
+    if f.argtypes is None:
+        vp, i, cp, i32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int32
+        f.argtypes = [vp, cp, i32, vp, vp, vp, i, i, i, i, vp, i, cp, cp, i, vp, vp, ctypes.c_int64, vp, vp, vp, vp, vp]
+    return f
 
 
 MSA_FORMATS = {"a3m": 0, "fasta": 1}
@@ -941,13 +950,20 @@ class Driver:
         cigars = [capi.cigar_string(cigar[int(r["cigar_offset"]):int(r["cigar_offset"]) + int(r["cigar_len"])]) for r in res]
         return res, cigars
 
-    def hit_msa(self, query_letters, result, max_identity=None, pssm=None, consensus=None, fmt="a3m", query_header="query"):
+    def hit_msa(self, query_letters, result, max_identity=None, pssm=None, consensus=None, fmt="a3m", query_header="query",
+                min_coverage=None, min_query_identity=None, diff=None, ladder=None):
         """The query-anchored multiple alignment of the hits of `result` (swdrv_hit_msa): the hits are aligned as
         align_hits aligns them — with `pssm` given as align_hits_pssm does, `query_letters` (or `consensus`) being the master —
         and the rows, residue counts and the greedy redundancy filter are computed on the GPU from what the aligner left there.
         max_identity: None (no filter) or 1 .. 100.
         -> dict: rows ((n + 1, qlen) uint8, row n the master; 0..19 residue, 20 other, 21 gap, 22 none), residues (n + 1),
-        keep (n + 1), purged, a3m (the text `align --outMsa` writes for the kept hits), results, cigars"""
+        keep (n + 1), purged, a3m (the text `align --outMsa` writes for the kept hits), results, cigars
+        With any of min_coverage (1 .. 100), min_query_identity (1 .. 100), diff (>= 1) or ladder (strictly ascending rungs)
+        the rows go through the selection of DESIGN.md §18 instead (swdrv_hit_msa_select): the ladder defaults to {max_identity}
+        and without max_identity to {100} under coverage / query identity alone (only a hit whose every residue repeats a kept
+        row is thinned), under diff to 20, 30, ... below max_identity (default 90) and then that.  The dict then also has
+        state (n + 1), depth (qlen), counts (kept hits, below coverage, below query identity, thinned) and ladder (the rungs
+        that were used); keep is state == 1 and purged counts the thinned hits."""
         import tempfile
         from . import capi, pssm as _pssm
         master = consensus if consensus is not None else query_letters
@@ -972,6 +988,41 @@ class Driver:
         residues = np.zeros(n + 1, dtype=np.int32)
         keep = np.zeros(n + 1, dtype=np.uint8)
         purged = ctypes.c_int32(0)
+        selecting = any(v is not None for v in (min_coverage, min_query_identity, diff, ladder))
+        if selecting:
+            from . import msa as _msa
+            C = 0 if min_coverage is None else int(min_coverage)
+            Q = 0 if min_query_identity is None else int(min_query_identity)
+            D = 0 if diff is None else int(diff)
+            if (min_coverage is not None and not 1 <= C <= 100) or (min_query_identity is not None and not 1 <= Q <= 100):
+                raise ValueError("min_coverage and min_query_identity must lie in [1, 100]")
+            if diff is not None and D < 1:
+                raise ValueError("diff must be at least 1")
+            if ladder is not None:
+                if max_identity is not None:
+                    raise ValueError("ladder and max_identity cannot be combined: the ladder's last rung is the cut")
+                rungs = _msa.check_ladder(ladder)
+            elif diff is not None:
+                rungs = _msa.default_ladder(P if max_identity is not None else 90)
+            else:   # coverage / query identity alone: max_identity, or the weakest cut the selection has
+                rungs = [P if max_identity is not None else 100]
+            state = np.zeros(n + 1, dtype=np.uint8)
+            depth = np.zeros(qlen, dtype=np.int32)
+            counts = np.zeros(4, dtype=np.int32)
+            lad = np.array(rungs, dtype=np.int32)
+            with tempfile.TemporaryDirectory() as tmp:
+                path = os.path.join(tmp, "hits." + fmt)
+                _check(_msa_select_fn()(self.handle, master, qlen, scored_with.ctypes.data if scored_with is not None else None,
+                                        ids.ctypes.data, scores.ctypes.data, n, C, Q, D, lad.ctypes.data, len(lad),
+                                        query_header.encode(), path.encode(), MSA_FORMATS[fmt], res.ctypes.data, cigar.ctypes.data,
+                                        cap, rows.ctypes.data, residues.ctypes.data, state.ctypes.data, depth.ctypes.data,
+                                        counts.ctypes.data))
+                with open(path) as f:
+                    text = f.read()
+            res = res[:n]
+            cigars = [capi.cigar_string(cigar[int(r["cigar_offset"]):int(r["cigar_offset"]) + int(r["cigar_len"])]) for r in res]
+            return {"rows": rows, "residues": residues, "keep": (state == 1).astype(np.uint8), "purged": int(counts[3]), "a3m": text,
+                    "results": res, "cigars": cigars, "state": state, "depth": depth, "counts": counts.tolist(), "ladder": rungs}
         with tempfile.TemporaryDirectory() as tmp:
             path = os.path.join(tmp, "hits." + fmt)
             _check(_msa_fns()[1](self.handle, master, qlen, scored_with.ctypes.data if scored_with is not None else None,

@@ -108,6 +108,84 @@ def greedy_keep(rows, max_identity, idents=None):
     return keep, purged
 
 
+STATE_NONE, STATE_KEPT, STATE_COVERAGE, STATE_QUERY_IDENTITY, STATE_THINNED = 0, 1, 2, 3, 4
+
+
+def check_ladder(ladder):
+    """-> the rungs as a list of ints: 1 .. 16 strictly ascending values in 1 .. 100"""
+    rungs = [int(p) for p in ladder]
+    if not 1 <= len(rungs) <= 16:
+        raise ValueError("the ladder needs 1 .. 16 rungs")
+    if any(not 1 <= p <= 100 for p in rungs) or any(b <= a for a, b in zip(rungs, rungs[1:])):
+        raise ValueError("the rungs must lie in [1, 100] and ascend strictly")
+    return rungs
+
+
+def default_ladder(last=90):
+    """the rungs `align --msaDiff` uses without --msaDiffLadder: 20, 30, ... below `last`, then `last`"""
+    return [p for p in range(20, 100, 10) if p < last] + [int(last)]
+
+
+def select_rows(rows, min_coverage=0, min_query_identity=0, diff=0, ladder=(90,)):
+    """the selection of sw_msa_select on rows ((n + 1, qlen) uint8, row n the master): a hit must have
+    min_coverage per cent of the query's positions aligned and be min_query_identity per cent identical to the master; the
+    rest are candidates, taken rung by rung of the ascending identity `ladder` in rank order: a candidate is kept when some
+    column of it still has fewer than `diff` kept residues (diff 0: always) and no kept row is similar to it at the rung.
+    -> (state (n + 1) uint8: 0 none, 1 kept, 2 below coverage, 3 below query identity, 4 thinned; depth (qlen) int32;
+    counts [kept hits, below coverage, below query identity, thinned]).
+    One pass over all rows per kept row: the time grows with kept rows x rows x qlen."""
+    rows = np.asarray(rows, dtype=np.uint8)
+    C, Q, D = int(min_coverage), int(min_query_identity), int(diff)
+    rungs = np.array(check_ladder(ladder), dtype=np.int64)
+    if not 0 <= C <= 100 or not 0 <= Q <= 100 or D < 0:
+        raise ValueError("min_coverage and min_query_identity must lie in [0, 100], diff must not be negative")
+    n, qlen = len(rows) - 1, rows.shape[1]
+    valid = rows < 20
+    res = valid.sum(axis=1).astype(np.int64)
+    state = np.zeros(n + 1, dtype=np.uint8)
+    depth = np.zeros(qlen, dtype=np.int32)
+    maxlev = np.zeros(n + 1, dtype=np.int64)   # the most rungs at which a kept row is similar to the row
+
+    def ident_to(g):
+        return ((rows == rows[g]) & valid).sum(axis=1).astype(np.int64)
+
+    def keep(g):
+        state[g] = STATE_KEPT
+        depth[valid[g]] += 1
+        similar = (100 * ident_to(g))[:, None] >= rungs[None, :] * res[:, None]
+        level = np.where(res > 0, similar.sum(axis=1), 0)
+        level[g] = 0
+        np.maximum(maxlev, level, out=maxlev)
+
+    candidates = []
+    if res[n] > 0:
+        keep(n)
+    to_master = ident_to(n) if Q > 0 else None
+    aligned = (rows <= 20).sum(axis=1).astype(np.int64)
+    for h in range(n):
+        if res[h] == 0:
+            continue
+        if 100 * aligned[h] < C * qlen:
+            state[h] = STATE_COVERAGE
+        elif Q > 0 and 100 * to_master[h] < Q * res[h]:
+            state[h] = STATE_QUERY_IDENTITY
+        else:
+            state[h] = STATE_THINNED
+            candidates.append(h)
+    for t in range(len(rungs)):
+        left = []
+        for h in candidates:
+            if D > 0 and not (depth[valid[h]] < D).any():
+                continue   # not needed now, so never again: depth only grows
+            if maxlev[h] > t:
+                left.append(h)
+                continue
+            keep(h)
+        candidates = left
+    counts = [int((state[:n] == s).sum()) for s in (STATE_KEPT, STATE_COVERAGE, STATE_QUERY_IDENTITY, STATE_THINNED)]
+    return state, depth, counts
+
+
 def format_a3m(query_letters, query_header, headers, subject_letters, results, cigars, keep=None, fmt="a3m"):
     """the text `align --outMsa` writes: the master, then every kept hit in rank order.  subject_letters: the hits' RAW
     letters; '=' / 'X' columns print them in upper case, 'I' columns '-', 'D' runs the letters in lower case (fmt 'fasta':

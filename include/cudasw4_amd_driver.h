@@ -252,6 +252,17 @@ int swdrv_hit_msa(swdrv* d, const char* master_letters, int32_t qlen, const int8
                   sw_align_result* results, uint32_t* cigar, int64_t cigar_cap, uint8_t* rows, int32_t* residues, uint8_t* keep,
                   int32_t* purged);
 
+/* swdrv_hit_msa with the selection of include/cudasw4_amd_msa_select.h in place of the greedy filter:
+ * min_coverage and min_query_identity in 0 .. 100 (0: no test), diff >= 0, ladder: n_ladder (1 .. 16) strictly ascending
+ * rungs in 1 .. 100; at most SW_MSA_SELECT_MAX_HITS hits.  Outputs, each optional: results / cigar / rows / residues as
+ * swdrv_hit_msa; state (n + 1 bytes: 0 none, 1 kept, 2 below coverage, 3 below query identity, 4 thinned), depth (qlen),
+ * counts (4: kept hits, below coverage, below query identity, thinned).  out_path: the hits with state 1 are written. */
+int swdrv_hit_msa_select(swdrv* d, const char* master_letters, int32_t qlen, const int8_t* pssm, const int64_t* ids,
+                         const int32_t* scores, int n, int min_coverage, int min_query_identity, int diff, const int32_t* ladder,
+                         int n_ladder, const char* query_header, const char* out_path, int format, sw_align_result* results,
+                         uint32_t* cigar, int64_t cigar_cap, uint8_t* rows, int32_t* residues, uint8_t* state, int32_t* depth,
+                         int32_t* counts);
+
 /* The writer alone (no GPU): '>' + query_header and the master's letters, then for every hit with keep[h] != 0 (keep NULL:
  * every hit) that is SW_ALIGN_OK with a CIGAR, in the given order, '>' + headers[h] and one line: '-' before q_begin; along
  * the CIGAR the subject's letter in upper case for '=' / 'X', '-' per 'I' column, the subject's letters in lower case for
